@@ -1,6 +1,6 @@
 """Benchmark: Mrays/s and ms/frame of the MobileRT render path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -20,7 +20,18 @@ C_wrapper.cpp:247-256), is `config.mrays_per_s_built`.  The frame buffer stays i
 memory; the reference's host-bitmap copy is excluded (DESIGN.md gives the PCIe-inclusive rate).
 The timed frames run with per-launch event timing OFF.
 
-Per-kernel roofline: outside the timed region one counting frame (node / triangle fetches per
+A plain run sets up, renders W warm-up frames, times K frames, writes its outputs if
+`--dump-outputs DIR` is given and prints the result line: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (one timed frame) and the workload's description.
+Everything else is measured only with `--full`: the per-kernel roofline, the frames copied to host
+memory, the median of five single frames, the committed PMC profile's traffic and the CPU
+baseline; a plain run reports those fields as null.
+
+`--dump-outputs DIR` writes what the last timed frame left with its caller (OUTPUTS below) as
+DIR/<name>.npy; the scene, the camera and every sample draw are fixed, so the same arguments give
+the same inputs in every run and two builds compare output for output.
+
+Per-kernel roofline (`--full`): outside the timed region one counting frame (node / triangle fetches per
 ray, shaded vertices) and two frames with the shadow stream serialised and HIP events around
 every launch give each kernel's average launch duration; `achieved` = algorithmic bytes per
 launch / that duration.
@@ -61,7 +72,12 @@ def parse():
     p.add_argument("--max-depth", type=int, default=5)
     p.add_argument("--shader", type=int, default=2)
     p.add_argument("--overlap", type=int, default=1, help="shadow rays on their own stream (timed frames)")
+    # everything beyond the headline figure: per-kernel roofline, host-copy and single-frame timings,
+    # PMC traffic, the CPU baseline (which --no-cpu-baseline leaves out of a --full run)
+    p.add_argument("--full", action="store_true")
     p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write the last timed frame's outputs as DIR/<name>.npy")
     # rehearsals (not the headline line): rank 0's shard of an N-GPU frame on this one GPU (e.g.
     # C5: --width 3840 --height 2160 --spp 8 --shard-of 8), and the final bitmap saved as .npy
     p.add_argument("--shard-of", type=int, default=0)
@@ -455,6 +471,88 @@ def kernel_roofline(r, step, overlap=1):
     return out, per_ray
 
 
+def roofline_report(args, shard_of, n_gpus, kernels, per_ray):
+    """The result line's `roofline` record (--full): kernel_roofline()'s per-kernel figures joined with
+    the committed PMC profile's traffic and issue counters, headed by the dominant kernel's."""
+    traffic, traffic_src = pmc_traffic(workload_key(args, shard_of)) if n_gpus == 1 else (
+        {}, {"status": "not collected for N > 1"})
+    counters = traffic_src.pop("counters", {})
+    for name, e in kernels.items():
+        tb = traffic.get(name)
+        e["traffic"] = tb
+        e["hbm_frac"] = (tb / (e["avg_launch_ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS) if tb and e["avg_launch_ms"] > 0 else None
+        # what bounds a walk that is not byte-bound: instruction issue (PMC, same profile as `traffic`)
+        e["issue"] = issue_fractions(counters[name]) if name in counters else None
+    dom = kernels["k_trace"]
+    return {
+        # the walk is bound by the per-CU vector-memory path serving divergent gathers of a
+        # cache-resident scene (PMC: texture-data unit busy ~92 %, bytes beyond L2 ~11 % of the
+        # algorithmic bytes; profiles/), not by HBM
+        "bound": "vmem-gather",
+        "kernel": "k_trace (closest hit, per-lane walk of depths %s)" % dom.get("depths"),
+        "achieved": dom["achieved"],
+        "peak": PEAK_VMEM_GBS,
+        "unit": "GB/s",
+        "frac": dom["frac"],
+        "traffic": dom["traffic"],
+        "traffic_source": traffic_src,
+        # the same launch priced at the bytes its loads request (16 B per quantized child record,
+        # 48 B per leaf record, 36 B per triangle test) instead of SURVEY 8(d)'s 32 B per record
+        "frac_fetched": dom["frac_fetched"],
+        "achieved_fetched": dom["achieved_fetched"],
+        "avg_launch_ms": dom["avg_launch_ms"],
+        "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"],
+        "per_ray": per_ray,
+        "peak_source": "MI355X microarchitecture figures: L2 34.5 TB/s aggregate, 36.9 TB/s with L1 reuse",
+        # measured on MI355X by tools/gather_ceiling.hip (profiles/r02_gather_ceiling.jsonl): dependent
+        # 64-byte record chains from a 32 MiB table, every lane at a different record vs every lane of
+        # a wave at the same one; the walk's rays sit between the two (coherent camera rays, scattered
+        # bounces)
+        "measured_ceilings_gbs": {"divergent_64B_records_32MiB": 6648.4, "wave_coherent_64B_records_32MiB": 27859.6},
+        "durations": "serialised frames (shadow stream off), HIP events on the render stream",
+        # the same kernel in the product frames (shadow walks beside it): slower per launch
+        "frac_overlapped": dom.get("frac_overlapped"),
+        "avg_launch_ms_overlapped": dom.get("avg_launch_ms_overlapped"),
+        # the rocprofv3 summaries these durations agree with (tools/final.sh): a run whose frames are
+        # all serialised (--overlap 0) for avg_launch_ms, the default run for the overlapped figure
+        "rocprof_summaries": {"serialised": "profiles/r06_kernel_stats_serial.csv",
+                              "product_frames": "profiles/r06_kernel_stats.csv"},
+        "kernels": kernels,
+    }
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: the most one run writes
+DUMP_SAMPLE_SEED = 20240607
+
+
+def frame_outputs(pixels, walked, shadow):
+    """OUTPUTS: the arrays of --dump-outputs, from the packed pixels the last timed frame wrote (the
+    whole bitmap, or the rank's packed shard with --shard-of) and that frame's ray counts.
+
+    `pixels` float32 (n, 4): the four bytes of every packed 32-bit pixel in memory order, 0 .. 255
+    (exact in float32, and a difference between two builds reads as a colour difference).  A frame
+    over the size limit is cut to a fixed, seeded sample of its pixels, in pixel order, and
+    `pixel_index` float64 (n,) then names the pixels kept.  `frame_rays` float64 (2,): the frame's
+    closest-hit walks and shadow rays (of several ranks, rank 0's share)."""
+    import numpy as np
+    px = np.ascontiguousarray(pixels, dtype=np.int32).view(np.uint8).reshape(-1, 4)
+    out = {"frame_rays": np.array([walked, shadow], dtype=np.float64)}
+    keep = (DUMP_LIMIT_BYTES - 4096) // (4 * 4 + 8)  # per pixel kept: four float32 and its float64 index
+    if px.shape[0] * 16 + 4096 > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(px.shape[0], size=keep, replace=False))
+        px = px[idx]
+        out["pixel_index"] = idx.astype(np.float64)
+    out["pixels"] = px.astype(np.float32)
+    return out
+
+
+def dump_outputs(directory, outputs):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     args = parse()
     import torch
@@ -540,14 +638,17 @@ def main():
     torch.cuda.synchronize()  # (the buffers' fills on torch's stream, before frames on the renderer's)
     for _ in range(args.warmup):
         step()
-    kernels, per_ray = kernel_roofline(r, step, args.overlap)
-    r.set_tuning(3, args.overlap)
+    kernels = per_ray = None
+    if args.full:
+        kernels, per_ray = kernel_roofline(r, step, args.overlap)
+        r.set_tuning(3, args.overlap)
 
     if dist_on:
         dist.barrier()
     torch.cuda.synchronize()
     rays0 = r.get_total_casted_rays()
     walked = 0  # closest-hit rays traversed + shadow rays: the rays whose walk ran
+    w = sr = 0
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -558,43 +659,51 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     rays = r.get_total_casted_rays() - rays0
+    # what the last timed frame left with its caller (the frames after this point render it again)
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        last = packed[:int(info["pixelSlots"])] if shard_of else bitmap
+        outputs = frame_outputs(last.cpu().numpy(), w, sr)
 
-    # BASELINE.md section 2's timed window ends with the bitmap in host memory: a second, shorter
-    # timed loop adds the D2H copy of the frame into pinned host memory to every frame
-    host_bm = torch.empty(bitmap.numel(), dtype=torch.int32, pin_memory=True) if rank == 0 else None
-    if dist_on:
-        dist.barrier()
-    k2 = max(1, min(args.steps, 10))
-    t2 = time.perf_counter()
-    for _ in range(k2):
-        step(sh)  # (on torch's stream: each frame after the previous frame's copy)
-        if rank == 0:
-            host_bm.copy_(bitmap, non_blocking=True)
-    torch.cuda.synchronize()
-    if dist_on:
-        dist.barrier()
-    d2h_ms = (time.perf_counter() - t2) / k2 * 1e3
-
-    # median of 5 frames, each timed alone (synchronised on both sides)
-    singles = []
-    for _ in range(5):
+    d2h_ms = median5_ms = None
+    if args.full:
+        # BASELINE.md section 2's timed window ends with the bitmap in host memory: a second, shorter
+        # timed loop adds the D2H copy of the frame into pinned host memory to every frame
+        host_bm = torch.empty(bitmap.numel(), dtype=torch.int32, pin_memory=True) if rank == 0 else None
         if dist_on:
             dist.barrier()
+        k2 = max(1, min(args.steps, 10))
+        t2 = time.perf_counter()
+        for _ in range(k2):
+            step(sh)  # (on torch's stream: each frame after the previous frame's copy)
+            if rank == 0:
+                host_bm.copy_(bitmap, non_blocking=True)
         torch.cuda.synchronize()
-        t3 = time.perf_counter()
-        step()
-        torch.cuda.synchronize()
-        singles.append((time.perf_counter() - t3) * 1e3)
-    median5_ms = sorted(singles)[2]
+        if dist_on:
+            dist.barrier()
+        d2h_ms = (time.perf_counter() - t2) / k2 * 1e3
+
+        # median of 5 frames, each timed alone (synchronised on both sides)
+        singles = []
+        for _ in range(5):
+            if dist_on:
+                dist.barrier()
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            singles.append((time.perf_counter() - t3) * 1e3)
+        median5_ms = sorted(singles)[2]
 
     if dist_on:
         red = "cpu" if backend == "gloo" else "cuda"
         t = torch.tensor([elapsed], dtype=torch.float64, device=red)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        t = torch.tensor([median5_ms], dtype=torch.float64, device=red)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        median5_ms = float(t.item())
+        if args.full:
+            t = torch.tensor([median5_ms], dtype=torch.float64, device=red)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            median5_ms = float(t.item())
         n = torch.tensor([rays, walked], dtype=torch.float64, device=red)
         dist.all_reduce(n, op=dist.ReduceOp.SUM)
         rays, walked = [int(x) for x in n.tolist()]
@@ -605,16 +714,6 @@ def main():
 
     frames = max(1, args.steps)
     n_gpus = len(group) if group else world
-    traffic, traffic_src = pmc_traffic(workload_key(args, shard_of)) if n_gpus == 1 else (
-        {}, {"status": "not collected for N > 1"})
-    counters = traffic_src.pop("counters", {})
-    for name, e in kernels.items():
-        tb = traffic.get(name)
-        e["traffic"] = tb
-        e["hbm_frac"] = (tb / (e["avg_launch_ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS) if tb and e["avg_launch_ms"] > 0 else None
-        # what bounds a walk that is not byte-bound: instruction issue (PMC, same profile as `traffic`)
-        e["issue"] = issue_fractions(counters[name]) if name in counters else None
-    dom = kernels["k_trace"]
     out = {
         "metric": BASELINE_METRIC,
         "value": walked / elapsed / 1e6,
@@ -658,47 +757,15 @@ def main():
             "value_counts": "walked rays (closest-hit walks run + shadow rays)",
             "event_timing_in_timed_frames": False,
         },
-        "roofline": {
-            # the walk is bound by the per-CU vector-memory path serving divergent gathers of a
-            # cache-resident scene (PMC: texture-data unit busy ~92 %, bytes beyond L2 ~11 % of the
-            # algorithmic bytes; profiles/), not by HBM
-            "bound": "vmem-gather",
-            "kernel": "k_trace (closest hit, per-lane walk of depths %s)" % dom.get("depths"),
-            "achieved": dom["achieved"],
-            "peak": PEAK_VMEM_GBS,
-            "unit": "GB/s",
-            "frac": dom["frac"],
-            "traffic": dom["traffic"],
-            "traffic_source": traffic_src,
-            # the same launch priced at the bytes its loads request (16 B per quantized child record,
-            # 48 B per leaf record, 36 B per triangle test) instead of SURVEY 8(d)'s 32 B per record
-            "frac_fetched": dom["frac_fetched"],
-            "achieved_fetched": dom["achieved_fetched"],
-            "avg_launch_ms": dom["avg_launch_ms"],
-            "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"],
-            "per_ray": per_ray,
-            "peak_source": "MI355X_MICROARCH.md: L2 34.5 TB/s aggregate, 36.9 TB/s with L1 reuse",
-            # measured on MI355X by tools/gather_ceiling.hip (profiles/r02_gather_ceiling.jsonl): dependent
-            # 64-byte record chains from a 32 MiB table, every lane at a different record vs every lane of
-            # a wave at the same one; the walk's rays sit between the two (coherent camera rays, scattered
-            # bounces)
-            "measured_ceilings_gbs": {"divergent_64B_records_32MiB": 6648.4, "wave_coherent_64B_records_32MiB": 27859.6},
-            "durations": "serialised frames (shadow stream off), HIP events on the render stream",
-            # the same kernel in the product frames (shadow walks beside it): slower per launch
-            "frac_overlapped": dom.get("frac_overlapped"),
-            "avg_launch_ms_overlapped": dom.get("avg_launch_ms_overlapped"),
-            # the rocprofv3 summaries these durations agree with (tools/final.sh): a run whose frames are
-            # all serialised (--overlap 0) for avg_launch_ms, the default run for the overlapped figure
-            "rocprof_summaries": {"serialised": "profiles/r06_kernel_stats_serial.csv",
-                                  "product_frames": "profiles/r06_kernel_stats.csv"},
-            "kernels": kernels,
-        },
+        "roofline": roofline_report(args, shard_of, n_gpus, kernels, per_ray) if args.full else None,
         "cpu_baseline": None,
         # the loaded library was built from the sources in this tree (Makefile stamp)
         "library_build_current": m._native.build_is_current(),
     }
-    if n_gpus == 1 and not shard_of and not args.no_cpu_baseline:
+    if args.full and n_gpus == 1 and not shard_of and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, scene)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     print(json.dumps(out), flush=True)
     if args.dump_bitmap:
         import numpy as np

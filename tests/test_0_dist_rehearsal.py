@@ -84,9 +84,19 @@ def test_group_bench_assembles_the_single_gpu_frame(tmp_path):
     import json
     import torch
     assert not torch.cuda.is_initialized(), "must run before this process touches the GPU"
-    one, _ = _bench(str(tmp_path), "one_g", 1)
+    # the plain run: the headline figure alone, and --dump-outputs holds the frame it timed
+    dump = str(tmp_path / "outputs")
+    one, line1 = _bench(str(tmp_path), "one_g", 1, extra_args=("--dump-outputs", dump))
+    j1 = json.loads(line1)
+    assert j1["ms_per_step"] > 0 and j1["value"] > 0 and j1["steps"] == 1
+    assert j1["roofline"] is None and j1["cpu_baseline"] is None and j1["ms_per_step_median5"] is None
+    px = np.load(os.path.join(dump, "pixels.npy"))
+    assert px.dtype == np.float32 and px.shape == (W * H, 4)
+    assert np.array_equal(px.astype(np.uint8).reshape(-1).view(np.int32), one)
+    fr = np.load(os.path.join(dump, "frame_rays.npy"))
+    assert fr.dtype == np.float64 and fr.sum() == j1["config"]["rays_walked_per_frame"]
     grp, line = _bench(str(tmp_path), "group", 4, launcher=False, extra_env={"MOBILERT_DEVICES": "0,0,0,0"},
-                       extra_args=("--path", "group", "--steps", "2", "--warmup", "1"))
+                       extra_args=("--path", "group", "--steps", "2", "--warmup", "1", "--full"))
     j = json.loads(line)
     assert j["n_gpus"] == 4 and j["config"]["parallelism"].startswith("device group x4"), j["config"]
     assert j["config"]["devices"] == [0, 0, 0, 0]

@@ -53,6 +53,32 @@ def test_cli_refuses_before_touching_a_gpu():
     assert p.returncode == 2 and "WORLD_SIZE=3" in p.stderr, p.stderr[-2000:]
 
 
+def test_dump_outputs_arrays(tmp_path):
+    """--dump-outputs: float arrays that hold the packed pixels exactly, whole below the size limit
+    and the same seeded sample above it, written as <name>.npy."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(1)
+    small = rng.integers(-2**31, 2**31, size=1000, dtype=np.int64).astype(np.int32)
+    out = bench.frame_outputs(small, 7, 3)
+    assert set(out) == {"pixels", "frame_rays"}
+    assert out["pixels"].dtype == np.float32 and out["pixels"].shape == (1000, 4)
+    assert np.array_equal(out["pixels"].astype(np.uint8).reshape(-1).view(np.int32), small)
+    assert out["frame_rays"].dtype == np.float64 and out["frame_rays"].tolist() == [7.0, 3.0]
+    n = bench.DUMP_LIMIT_BYTES // 16 + 1  # one pixel more than fits whole
+    big = np.arange(n, dtype=np.int32)
+    a, b = bench.frame_outputs(big, 0, 0), bench.frame_outputs(big, 0, 0)
+    idx = a["pixel_index"]
+    assert np.array_equal(idx, b["pixel_index"]) and np.array_equal(a["pixels"], b["pixels"])
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+    assert np.array_equal(a["pixels"].astype(np.uint8).reshape(-1).view(np.int32), big[idx.astype(np.int64)])
+    bench.dump_outputs(str(tmp_path / "d"), a)
+    files = sorted(os.listdir(tmp_path / "d"))
+    assert files == ["frame_rays.npy", "pixel_index.npy", "pixels.npy"]
+    assert 0.9 * bench.DUMP_LIMIT_BYTES < sum(os.path.getsize(tmp_path / "d" / f) for f in files) <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(np.load(tmp_path / "d" / "pixels.npy"), a["pixels"])
+
+
 def test_group_path_runs_in_one_process():
     from bench import group_devices
     # --path group: one process for the whole device group, never spawned

@@ -11,7 +11,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   [ $rc -ne 0 ] && exit $rc
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-  timeout -k 10 300 python bench.py ${BENCH_ARGS:---no-cpu-baseline} > $OUT/bench.log 2>&1 || { echo bench failed; tail $OUT/bench.log; exit 4; }
+  timeout -k 10 300 python bench.py --full ${BENCH_ARGS:---no-cpu-baseline} > $OUT/bench.log 2>&1 || { echo bench failed; tail $OUT/bench.log; exit 4; }
   tail -1 $OUT/bench.log > $OUT/bench.json; cut -c1-400 $OUT/bench.json
 fi
 if [ -n "${THEN:-}" ]; then bash -c "$THEN" || exit 5; fi

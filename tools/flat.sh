@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"; R=$(pwd)
 N=${1:-flat}; OUT=$R/gpurun_out/$N; mkdir -p $OUT
 export PYTHONUNBUFFERED=1
 python -c "from mobileraytracer_amd import _native as n; assert n.build_is_current(), 'stale libmobilert_amd.so'" || exit 2
-timeout -k 10 200 python bench.py --scene flat --no-cpu-baseline > $OUT/flat.log 2>&1 || { tail $OUT/flat.log; exit 3; }
+timeout -k 10 200 python bench.py --full --scene flat --no-cpu-baseline > $OUT/flat.log 2>&1 || { tail $OUT/flat.log; exit 3; }
 tail -1 $OUT/flat.log > $OUT/flat.json; cut -c1-300 $OUT/flat.json
 timeout -k 10 300 python tools/phase_occupancy.py conference flat > $OUT/phases.jsonl 2>$OUT/phases.err || { tail $OUT/phases.err; exit 4; }
 cut -c1-300 $OUT/phases.jsonl

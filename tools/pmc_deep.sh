@@ -2,7 +2,7 @@
 # Memory-pipeline PMC passes (TA / TD / TCP) on the closest-hit trace kernel, one group per run.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; R=$(pwd); OUT=$R/gpurun_out/${1:-pmc_deep}; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+CMD="python $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline"
 i=0
 for grp in "GRBM_GUI_ACTIVE TA_TA_BUSY TD_TD_BUSY" "TCP_TOTAL_CACHE_ACCESSES TCP_TCC_READ_REQ TCP_PENDING_STALL_CYCLES" \
            "TCP_TCP_LATENCY TCP_TCC_READ_REQ_LATENCY" "TA_ADDR_STALLED_BY_TC_CYCLES TA_DATA_STALLED_BY_TC_CYCLES TA_FLAT_READ_WAVEFRONTS" \
