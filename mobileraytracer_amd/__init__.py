@@ -130,8 +130,10 @@ class Renderer:
         16 = the camera rays' packet walk (cull modes 0 and 3; refused when the walk tree needs a
         deeper stack than the packet walk's), 17 = level 1 fused (camera rays generated,
         packet-walked and shaded in one launch), 19-23 = the tile kernel and its knobs, 27 = the
-        last shadow walk on the render stream.  Results are identical for every value, except
-        key 2 = 1 (documented inexact)."""
+        last shadow walk on the render stream, 37 = byte budget of the wavefront queues in MiB
+        (0 automatic), 38 = the first allocation's deeper levels in percent of level 1 (200),
+        39 = slack slots per queue segment (3072); 37-39 reallocate the queues from the next frame.
+        Results are identical for every value, except key 2 = 1 (documented inexact)."""
         _native.check(self._lib.mrt_set_tuning(self._h, key, value))
 
     def set_camera(self, kind: int, position, look_at, up, a: float, b: float) -> None:
@@ -172,6 +174,17 @@ class Renderer:
         for k in ("levelNodeRecords", "levelTriTests", "levelLeafRecords", "levelShadedVertices", "walkPhases",
                   "packetWaveRecords"):
             out[k] = list(getattr(s, k))
+        return out
+
+    def queue_info(self) -> dict:
+        """mrt_get_queue_info: the wavefront queues' plan (chunkSlots, passes per sample set, queueBytes,
+        budgetBytes, replans since creation and during the last frame, worstCase, per depth rayCap /
+        shadowCap) and what the last pass asked of them (requestedRays / requestedShadows)."""
+        q = _native.MrtQueueInfo()
+        _native.check(self._lib.mrt_get_queue_info(self._h, ctypes.byref(q), ctypes.sizeof(q)))
+        out = {f: getattr(q, f) for f, _ in q._fields_}
+        for k in ("rayCap", "shadowCap", "requestedRays", "requestedShadows"):
+            out[k] = list(getattr(q, k))
         return out
 
     def frame_rays(self):
@@ -255,6 +268,46 @@ def triangle_bvh(config: Config):
     if n2 != n:
         raise RuntimeError(lib.mrt_last_error().decode())
     return boxes, off, cnt, order[:int(cnt[0])] if n == 1 else order
+
+
+def plan_queues(levels: int, branching: int, pixel_slots: int, samples_pixel: int = 1, samples_light: int = 1,
+                textured: bool = False, path_budget: int = 0, byte_budget: int = 0, growth_pct: int = 0,
+                slack: int = -1, worst_case: bool = False, demand: Optional[dict] = None,
+                previous: Optional[dict] = None) -> dict:
+    """The renderer's queue planner (mrt_plan_queues, host only; DESIGN.md section 2, "Queue plans").
+
+    Without ``demand``: the first allocation.  ``demand`` is the record of an overflowed pass:
+    ``{"mask": bit l = depth l's queue dropped a write, "chunkSlots", "paths": level-1 paths of
+    that chunk, "seg": per depth the largest segment's requested rays, "shadowSeg": ... shadow
+    rays}``.  ``previous`` is the plan that pass ran with (a dict as returned here): no capacity
+    per path shrinks.  ``worst_case``: every level holds all the rays a chunk can spawn.
+    Returns ``{"chunkSlots", "segCap", "shadowSegCap", "bytes", "worstCase"}`` (the lists: one
+    entry per level, slots per queue segment; a queue is 8 segments).  Raises RuntimeError when no
+    chunk fits the byte budget."""
+    q = _native.MrtQueuePlanRequest()
+    q.levels, q.branching, q.samplesPixel, q.samplesLight = levels, branching, samples_pixel, samples_light
+    q.textured, q.segments, q.growthPct, q.slack = int(textured), 0, growth_pct, slack
+    q.worstCase, q.pixelSlots, q.pathBudget, q.byteBudget = int(worst_case), pixel_slots, path_budget, byte_budget
+    if demand is not None:
+        q.hasDemand = 1
+        q.overflowMask = int(demand["mask"])
+        q.demandChunkSlots = int(demand["chunkSlots"])
+        q.demandPaths = int(demand["paths"])
+        for i, v in enumerate(demand["seg"]):
+            q.segDemand[i] = int(v)
+        for i, v in enumerate(demand["shadowSeg"]):
+            q.shadowSegDemand[i] = int(v)
+    if previous is not None:
+        q.prevChunkSlots = int(previous["chunkSlots"])
+        for i, v in enumerate(previous["segCap"]):
+            q.prevSegCap[i] = int(v)
+        for i, v in enumerate(previous["shadowSegCap"]):
+            q.prevShadowSegCap[i] = int(v)
+    plan = _native.MrtQueuePlan()
+    _native.check(_native.lib().mrt_plan_queues(ctypes.byref(q), ctypes.byref(plan)))
+    return {"chunkSlots": int(plan.chunkSlots), "segCap": list(plan.segCap)[:levels],
+            "shadowSegCap": list(plan.shadowSegCap)[:levels], "bytes": int(plan.bytes),
+            "worstCase": bool(plan.worstCase)}
 
 
 def regular_grid(config: Config, kind: int):

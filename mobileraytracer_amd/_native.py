@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = (
     "mrt_android_stop_render", "mrt_android_finish_render", "mrt_android_state", "mrt_android_fps",
     "mrt_android_time_renderer", "mrt_android_sample", "mrt_android_number_of_lights", "mrt_android_resize",
     "mrt_android_vertices", "mrt_android_colors", "mrt_android_camera", "mrt_android_reset",
+    "mrt_get_queue_info", "mrt_plan_queues",
     "RayTrace", "stopRender",
 )
 
@@ -81,6 +82,33 @@ class MrtFrameStats(ctypes.Structure):
     ]
 
 
+QUEUE_LEVELS = 16  # MRT_QUEUE_LEVELS
+
+
+class MrtQueueInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "chunkSlots", "passes", "queueBytes", "budgetBytes", "replans", "replansLastFrame", "worstCase")] + [
+        (n, ctypes.c_int64 * QUEUE_LEVELS) for n in ("rayCap", "shadowCap", "requestedRays", "requestedShadows")]
+
+
+class MrtQueuePlanRequest(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "levels", "branching", "samplesPixel", "samplesLight", "textured", "segments", "growthPct", "slack",
+        "worstCase", "hasDemand")] + [
+        ("pixelSlots", ctypes.c_int64), ("pathBudget", ctypes.c_int64), ("byteBudget", ctypes.c_int64),
+        ("overflowMask", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("demandChunkSlots", ctypes.c_int64), ("demandPaths", ctypes.c_int64),
+        ("segDemand", ctypes.c_int64 * QUEUE_LEVELS), ("shadowSegDemand", ctypes.c_int64 * QUEUE_LEVELS),
+        ("prevChunkSlots", ctypes.c_int64),
+        ("prevSegCap", ctypes.c_int64 * QUEUE_LEVELS), ("prevShadowSegCap", ctypes.c_int64 * QUEUE_LEVELS)]
+
+
+class MrtQueuePlan(ctypes.Structure):
+    _fields_ = [("chunkSlots", ctypes.c_int64), ("segCap", ctypes.c_int64 * QUEUE_LEVELS),
+                ("shadowSegCap", ctypes.c_int64 * QUEUE_LEVELS), ("bytes", ctypes.c_int64),
+                ("worstCase", ctypes.c_int64)]
+
+
 def _preload_torch_hip_runtime():
     """One HIP runtime per process: if PyTorch-ROCm is installed, load its libamdhip64 first
     (by full path, without importing torch) so this library and torch share it whichever is
@@ -117,6 +145,8 @@ def load_library(path=LIB_PATH):
         "mrt_get_scene_info": (ctypes.c_int, [vp, P(MrtSceneInfo)]),
         "mrt_set_profiling": (ctypes.c_int, [vp, ctypes.c_int32]),
         "mrt_get_frame_stats": (ctypes.c_int, [vp, P(MrtFrameStats)]),
+        "mrt_get_queue_info": (ctypes.c_int, [vp, vp, ctypes.c_size_t]),
+        "mrt_plan_queues": (ctypes.c_int, [P(MrtQueuePlanRequest), P(MrtQueuePlan)]),
         "mrt_wave_log": (ctypes.c_int64, [vp, vp]),
         "mrt_primary_hits": (ctypes.c_int, [vp, vp, vp, vp]),
         "mrt_set_tuning": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int32]),
@@ -179,9 +209,10 @@ def source_stamp():
     """The digest the Makefile embeds (mrt_build_stamp) for the csrc sources in this tree."""
     import hashlib
     d = os.path.join(_HERE, "csrc")
-    srcs = ["mrt_scene.cpp", "mrt_grid.cpp", "mrt_texture.cpp", "mrt_android.cpp", "mrt_kernels.hip", "mrt_renderer.hip",
+    srcs = ["mrt_scene.cpp", "mrt_grid.cpp", "mrt_texture.cpp", "mrt_android.cpp", "mrt_queue_plan.cpp", "mrt_kernels.hip",
+            "mrt_renderer.hip",
             "mrt_common.hpp", "mrt_device.hpp", "mrt_kernels.hpp", "mrt_trace_ww.hpp", "mrt_trace_packet.hpp",
-            "mrt_scene.hpp", "../../include/mobilert_amd.h", "../../include/mobilert_amd.hpp",
+            "mrt_scene.hpp", "mrt_queue_plan.hpp", "../../include/mobilert_amd.h", "../../include/mobilert_amd.hpp",
             "../../include/mobilert_android.h"]
     h = hashlib.sha256()
     for f in srcs:

@@ -620,14 +620,15 @@ __device__ __forceinline__ ShadeState shadePrepare(const DScene& s, float4 o4, f
 }
 
 // Writes vertex i's shadow rays (level lv, from shadowBase) and children (level nx, from
-// childBase) and its record.  Slots past a queue's capacity set the overflow flag (the frame is
-// then redone in smaller passes).  deadNext: level + 1 is the depth-capped last level, whose
+// childBase) and its record.  Slots past a queue's capacity set the overflow flag - the bit of the
+// level whose queue dropped the write: `level` for a shadow ray, level + 1 for a child (the pass is
+// then redone with queues planned from its demand, k_tally).  deadNext: level + 1 is the depth-capped last level, whose
 // rays are counted (the reference constructs them) but never traced, shaded or read, so their
 // payloads are not written and their directions not computed.
 // shadowEnd / childEnd: the end of the queue segments the bases lie in (slots from there on overflow)
 __device__ __forceinline__ void shadeEmit(const DScene& s, const ShadeState& v, int i, const Level& lv, const Level& nx,
                                           int shadowBase, int childBase, int shadowEnd, int childEnd, int* counters,
-                                          const ShadeArgs& a, bool deadNext, const float4* lights) {
+                                          const ShadeArgs& a, bool deadNext, const float4* lights, int level) {
     if (v.terminal) {
         lv.res[i] = v.leaf;
         lv.vtx[i] = make_int4(-1, 0, 0, 0);
@@ -653,7 +654,7 @@ __device__ __forceinline__ void shadeEmit(const DScene& s, const ShadeState& v, 
                 lv.sD[j] = make_float4(ld.x, ld.y, ld.z, dist);
                 lv.sC[j] = make_float4(lc.x, lc.y, lc.z, 0.0F);
             } else {
-                atomicOr(counters + kCntOverflow, 1);
+                atomicOr(counters + kCntOverflow, 1 << level);
             }
         }
     }
@@ -664,7 +665,7 @@ __device__ __forceinline__ void shadeEmit(const DScene& s, const ShadeState& v, 
         auto emit = [&](v3 dir, uint32_t slot) {
             const int j = c++;
             if (j >= childEnd) {
-                atomicOr(counters + kCntOverflow, 1);
+                atomicOr(counters + kCntOverflow, 2 << level);
                 return;
             }
             nx.rO[j] = make_float4(v.g.P.x, v.g.P.y, v.g.P.z, bitsf(v.key));
@@ -753,7 +754,7 @@ __global__ __launch_bounds__(kBlock) void k_shade(DScene s, Level lv, Level nx, 
         parity ^= 1;
         if (active)
             shadeEmit(s, v, i, lv, nx, shadowOff + shadowBase, childOff + childBase, shadowOff + lv.shadowSegCap,
-                      childOff + nx.segCap, counters, a, dead, lights);
+                      childOff + nx.segCap, counters, a, dead, lights, level);
         if (kFull && a.stats != nullptr) {  // counting pass: shaded (non-terminal) vertices
             const uint64_t m = __ballot(active && !v.terminal);
             if (laneId() == 0 && m != 0) {
@@ -811,7 +812,7 @@ struct PacketShade {
         const int childOff = seg * nx.segCap, shadowOff = seg * lv.shadowSegCap;
         if (valid)
             shadeEmit(*s, v, i, lv, nx, shadowOff + shadowBase, childOff + childBase, shadowOff + lv.shadowSegCap,
-                      childOff + nx.segCap, counters, a, dead, s->lights);
+                      childOff + nx.segCap, counters, a, dead, s->lights, level);
     }
 };
 
@@ -1093,18 +1094,33 @@ __global__ __launch_bounds__(256) void k_tally(int* counters, int maxLevel, unsi
     if (threadIdx.x == 0) {
         unsigned long long rays = 0, shadows = 0;
         // a level's rays: the sum over its queue segments (the capped last level's are counted, never written)
-        auto levelRays = [&](int l, bool sh) {
-            unsigned long long n = 0;
-            for (int g = 0; g < kQueueSegs; ++g)
-                n += static_cast<unsigned long long>(counters[sh ? cntShadows(l, g) : cntRays(l, g)]);
+        // *most: the largest segment's count
+        auto levelRays = [&](int l, bool sh, unsigned long long* most = nullptr) {
+            unsigned long long n = 0, m = 0;
+            for (int g = 0; g < kQueueSegs; ++g) {
+                const auto c = static_cast<unsigned long long>(counters[sh ? cntShadows(l, g) : cntRays(l, g)]);
+                n += c;
+                m = c > m ? c : m;
+            }
+            if (most != nullptr) *most = m;
             return n;
         };
+        // a statistic that keeps the largest value of the pass's chunks
+        auto keepMost = [&](int k, unsigned long long v) {
+            if (v > stats[k]) stats[k] = v;
+        };
         for (int l = 1; l <= maxLevel; ++l) {
-            const unsigned long long r = levelRays(l, false), sh = levelRays(l, true);
+            unsigned long long mr, ms;
+            const unsigned long long r = levelRays(l, false, &mr), sh = levelRays(l, true, &ms);
             rays += r;
             shadows += sh;
             stats[kStatLevelRays + l - 1] += r;
             stats[kStatLevelShadows + l - 1] += sh;
+            // the demand record (kStatReq*): the counters run past a full segment
+            keepMost(kStatReqSegRays + l - 1, mr);
+            keepMost(kStatReqSegShadows + l - 1, ms);
+            keepMost(kStatReqRays + l - 1, r);
+            keepMost(kStatReqShadows + l - 1, sh);
         }
         stats[kStatRays] += rays;
         stats[kStatShadowRays] += shadows;

@@ -76,7 +76,17 @@ constexpr int kStatPhases = kStatOccluded + 1;  // counting pass: 2 walks x {inn
 // counting pass, the level-1 packet walk, per wave (scalar loads: each record fetched once for the
 // wave's rays): inner nodes visited, leaf records loaded, triangle records loaded
 constexpr int kStatPacket = kStatPhases + 16;
-constexpr int kNumStats = kStatPacket + 3;
+// What the pass asked of its queues (k_tally; + level - 1), the largest over the pass's chunks: the
+// largest count one segment of the level's ray / shadow queue was asked for, and the level's total.
+// The allocation counters run past a full segment (only the writes are dropped), so after an
+// overflow these are the demand the next queue plan is sized from (mrt_queue_plan.hpp): exact up to
+// the first overflowed level (kStatOverflow: bit l = level l's ray or shadow queue dropped a write),
+// lower bounds below it.
+constexpr int kStatReqSegRays = kStatPacket + 3;
+constexpr int kStatReqSegShadows = kStatReqSegRays + kMaxLevels;
+constexpr int kStatReqRays = kStatReqSegShadows + kMaxLevels;
+constexpr int kStatReqShadows = kStatReqRays + kMaxLevels;
+constexpr int kNumStats = kStatReqShadows + kMaxLevels;
 // counting builds: per walk launch (closest / any-hit x level) and wave {start, end (100 MHz
 // ticks), rays fetched, child records fetched}, after the statistics (mrt_wave_log)
 constexpr int kWaveLogWaves = 8192;

@@ -26,6 +26,7 @@
 #include "mobilert_amd.h"
 #include "mobilert_amd.hpp"
 #include "mrt_kernels.hpp"
+#include "mrt_queue_plan.hpp"
 #include "mrt_scene.hpp"
 
 namespace {
@@ -350,6 +351,22 @@ struct mrt_renderer {
         size_t evCount = 0;
     } pipe;
     int chunkSlots = 0;
+    // The queue plan in use (mrt_queue_plan.hpp) and what it was made from.  It stays with the
+    // renderer: a plan learned from an overflowed pass serves the later frames.
+    mrt_queue_plan plan{};
+    int64_t planBudget = 0;              // the byte budget the plan was made for
+    int queueBudgetMiB = 0;              // tuning key 37: 0 automatic (half of the free device memory)
+    int queueGrowthPct = mrt::kPlanGrowthPct;  // tuning key 38: the first allocation's deeper levels
+    int queueSlack = mrt::kPlanSlack;    // tuning key 39: fixed slots per segment
+    int deviceShare = 1;                 // shards of the device group on this renderer's GPU (the budget's divisor)
+    bool planStale = false;              // a key above changed: first allocation again before the next pass
+    int64_t replans = 0, replansFrame = 0;  // plans made after an overflowed pass: ever, this frame
+    // the last pass's demand record (k_tally's kStatReq*): per level the largest segment's count and
+    // the total, for rays and shadow rays; the overflow mask; the paths of its (largest) chunk
+    int64_t reqSegRays[mrt::kMaxLevels] = {}, reqSegShadows[mrt::kMaxLevels] = {};
+    int64_t reqRays[mrt::kMaxLevels] = {}, reqShadows[mrt::kMaxLevels] = {};
+    int overflowMask = 0;
+    int64_t reqPaths = 0;
     int gdepth = 0;
     int traceThreads = 0, workGrid = 0;  // traceThreads: resident trace threads, whole device
     int cus = 0;
@@ -735,14 +752,11 @@ void setPixelSampler(const mrt_renderer* r, mrt::RaygenArgs* ra) {
     ra->constJitter = r->pixelSampler == 0 ? r->pixelConst : 0.5F;
 }
 
-void allocQueues(mrt_renderer* r, int chunkSlots, int growth) {
+// The wavefront queues of r->plan (planFirst / planAfterOverflow).
+void allocQueues(mrt_renderer* r) {
     using namespace mrt;
     r->queueMem.release();
-    const int spp = std::max(1, r->cfg.samplesPixel);
-    const int spl = std::max(1, r->cfg.samplesLight);
-    r->chunkSlots = chunkSlots;
-    const size_t n1 = static_cast<size_t>(chunkSlots) * static_cast<size_t>(spp);
-    const size_t capN = n1 * static_cast<size_t>(growth);
+    r->chunkSlots = static_cast<int>(r->plan.chunkSlots);
     const int nLevels = r->nLevels;
     r->gdepth = std::max(1, r->stackNeed - kLdsStackMin);
     mrt_renderer::Pipe& pp = r->pipe;
@@ -753,19 +767,11 @@ void allocQueues(mrt_renderer* r, int chunkSlots, int growth) {
         Level& lv = pp.levels[l];
         const bool real = l <= nLevels;
         // Queue segments (mrt_kernels.hpp): level 1 is its dense paths cut into kQueueSegs pieces;
-        // a deeper level's segments each hold an eighth of the level's rays plus slack for the uneven
-        // split over the shading workgroups (an overflow re-renders with smaller chunks, as before)
-        size_t segCap, shadowSegCap;
-        if (kQueueSegs == 1) {
-            segCap = (l == 1) ? n1 : capN;
-            shadowSegCap = segCap * spl;
-        } else if (l == 1) {
-            segCap = (n1 + kQueueSegs - 1) / kQueueSegs;
-            shadowSegCap = (n1 * spl * 5 / 4 + kQueueSegs - 1) / kQueueSegs + static_cast<size_t>(spl) * 4 * 256;
-        } else {
-            segCap = (capN * 5 / 4 + kQueueSegs - 1) / kQueueSegs + 3 * 4 * 256;
-            shadowSegCap = (capN * spl * 5 / 4 + kQueueSegs - 1) / kQueueSegs + static_cast<size_t>(spl) * 4 * 256;
-        }
+        // a deeper level's segments are sized by the plan (the first: an eighth of twice level 1
+        // plus slack for the uneven split over the shading workgroups; after an overflow: what the
+        // pass asked for).  (Level nLevels + 1, not real: the sizes of level nLevels, unused.)
+        const size_t segCap = static_cast<size_t>(r->plan.segCap[std::min(l, nLevels) - 1]);
+        const size_t shadowSegCap = static_cast<size_t>(r->plan.shadowSegCap[std::min(l, nLevels) - 1]);
         const size_t cap = segCap * kQueueSegs;
         lv = Level{};
         lv.cap = real ? static_cast<int>(cap) : 0;
@@ -836,12 +842,80 @@ void createShadowStream(mrt_renderer* r) {
     r->overlap = 0;
 }
 
-// Chunk size: every slot of the shard in one pass, within the path budget.
-int chunkFor(const mrt_renderer* r) {
-    const size_t spp = static_cast<size_t>(std::max(1, r->cfg.samplesPixel));
-    const size_t maxPaths = r->cfg.maxPathsPerPass > 0 ? static_cast<size_t>(r->cfg.maxPathsPerPass) : (size_t{1} << 24);
-    return static_cast<int>(std::max<size_t>(1, std::min(static_cast<size_t>(r->nSlots), maxPaths / spp)));
+// ---- queue plans (mrt_queue_plan.hpp) ---------------------------------------------------------
+// What the planner needs to know of this renderer.  The chunk: every slot of the shard in one pass,
+// within the path budget (maxPathsPerPass) and the byte budget: tuning key 37, else half of the
+// device memory free once the current queues are released.  Frees nothing: a plan that fails
+// leaves the renderer with the queues it had.
+mrt_queue_plan_request planRequest(mrt_renderer* r) {
+    using namespace mrt;
+    mrt_queue_plan_request q{};
+    q.levels = r->nLevels;
+    q.branching = r->shader == kShaderWhitted ? 2 : r->shader == kShaderPathTracer ? 3 : 1;
+    q.samplesPixel = std::max(1, r->cfg.samplesPixel);
+    q.samplesLight = std::max(1, r->cfg.samplesLight);
+    q.textured = r->ds.textured != 0 ? 1 : 0;
+    q.segments = kQueueSegs;
+    q.growthPct = r->queueGrowthPct;
+    q.slack = r->queueSlack;
+    q.pixelSlots = std::max(1, r->nSlots);
+    q.pathBudget = r->cfg.maxPathsPerPass > 0 ? r->cfg.maxPathsPerPass : kPlanPathBudget;
+    if (r->queueBudgetMiB > 0) {
+        q.byteBudget = static_cast<int64_t>(r->queueBudgetMiB) << 20;
+    } else {
+        // free now, plus the queues this plan replaces (allocQueues releases them first); shards of
+        // a device group that share the GPU share the half
+        size_t freeBytes = 0, totalBytes = 0;
+        MRT_HIP(hipMemGetInfo(&freeBytes, &totalBytes));
+        const size_t avail = (freeBytes + r->queueMem.total) / 2 / static_cast<size_t>(std::max(1, r->deviceShare));
+        q.byteBudget = std::max<int64_t>(1, static_cast<int64_t>(avail));
+    }
+    return q;
 }
+
+// Makes the plan of q the renderer's and allocates its queues.  A plan that fits no chunk falls
+// back to the worst-case plan, whose slack-free queues are the smallest that cannot overflow; if
+// that does not fit either, one pixel's ray tree is too large for the budget.
+void adoptPlan(mrt_renderer* r, mrt_queue_plan_request q) {
+    std::string err;
+    mrt_queue_plan plan{};
+    if (!mrt::planQueues(q, &plan, &err)) {
+        if (q.worstCase != 0) throw std::runtime_error(err);
+        q.worstCase = 1;
+        if (!mrt::planQueues(q, &plan, &err)) throw std::runtime_error(err);
+    }
+    r->plan = plan;
+    r->planBudget = q.byteBudget;
+    r->planStale = false;
+    allocQueues(r);
+}
+
+// The first allocation.
+void planFirst(mrt_renderer* r) { adoptPlan(r, planRequest(r)); }
+
+// After an overflowed pass (runPass kept its demand record): demand-driven plans for the first
+// kPlanDemandRetries retries of a frame, then the worst-case plan, which cannot overflow.
+void planAfterOverflow(mrt_renderer* r, int retry) {
+    using namespace mrt;
+    if (r->plan.worstCase != 0) throw std::runtime_error("wavefront queue overflow under the worst-case queue plan");
+    mrt_queue_plan_request q = planRequest(r);
+    q.worstCase = retry >= kPlanDemandRetries ? 1 : 0;
+    q.hasDemand = 1;
+    q.overflowMask = r->overflowMask;
+    q.demandChunkSlots = r->plan.chunkSlots;
+    q.demandPaths = r->reqPaths;
+    q.prevChunkSlots = r->plan.chunkSlots;
+    for (int l = 0; l < kMaxLevels; ++l) {
+        q.segDemand[l] = r->reqSegRays[l];
+        q.shadowSegDemand[l] = r->reqSegShadows[l];
+        q.prevSegCap[l] = r->plan.segCap[l];
+        q.prevShadowSegCap[l] = r->plan.shadowSegCap[l];
+    }
+    adoptPlan(r, q);
+    ++r->replans;
+    ++r->replansFrame;
+}
+static_assert(mrt::kPlanLevels == mrt::kMaxLevels && mrt::kPlanSegments == 8, "queue plan: the library's levels");
 
 hipEvent_t syncEvent(mrt_renderer::Pipe& p, size_t i) {
     while (p.syncPool.size() <= i) {
@@ -1062,12 +1136,22 @@ void renderPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t
 bool runPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t st, int sampleBase, int spp,
              mrt_frame_stats* fs) {
     using namespace mrt;
+    if (r->planStale) planFirst(r);  // (tuning keys 37-39 changed)
     const auto t0 = std::chrono::steady_clock::now();
     renderPass(r, dBitmap, dPacked, st, sampleBase, spp);
     MRT_HIP(hipStreamSynchronize(st));  // (k_tally wrote the pass's statistics into r->hostStats)
     unsigned long long hs[kNumStats];
     std::memcpy(hs, r->hostStats, sizeof(hs));
     const auto t1 = std::chrono::steady_clock::now();
+    // what the pass asked of its queues: mrt_get_queue_info, and after an overflow the next plan
+    for (int l = 0; l < kMaxLevels; ++l) {
+        r->reqSegRays[l] = static_cast<int64_t>(hs[kStatReqSegRays + l]);
+        r->reqSegShadows[l] = static_cast<int64_t>(hs[kStatReqSegShadows + l]);
+        r->reqRays[l] = static_cast<int64_t>(hs[kStatReqRays + l]);
+        r->reqShadows[l] = static_cast<int64_t>(hs[kStatReqShadows + l]);
+    }
+    r->overflowMask = static_cast<int>(hs[kStatOverflow]);
+    r->reqPaths = static_cast<int64_t>(std::min(r->chunkSlots, std::max(1, r->nSlots))) * spp;
     if (hs[kStatOverflow] != 0) return false;
     fs->rays += hs[kStatRays];
     fs->shadowRays += hs[kStatShadowRays];
@@ -1162,7 +1246,7 @@ void addStats(mrt_frame_stats& a, const mrt_frame_stats& b) {
 }
 
 // Progressive mode: sample smp's pass, its statistics added to *fs.  The running average is read
-// by the pass: a copy is kept to redo a pass whose queues overflowed (in smaller chunks).
+// by the pass: a copy is kept to redo a pass whose queues overflowed (with replanned queues).
 void renderProgressiveSample(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t st, int smp,
                              mrt_frame_stats* fs) {
     const size_t npx = static_cast<size_t>(r->cfg.width) * static_cast<size_t>(r->cfg.height);
@@ -1172,7 +1256,9 @@ void renderProgressiveSample(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked
         r->dBackup = r->frameMem.alloc<int32_t>(accN);
         r->backupN = accN;
     }
-    for (int attempt = 0; attempt < 4; ++attempt) {
+    // (at most kPlanDemandRetries demand-driven plans, then the worst-case plan, which cannot overflow:
+    // planAfterOverflow throws if it did)
+    for (int retry = 0;; ++retry) {
         if (acc != nullptr) MRT_HIP(hipMemcpyAsync(r->dBackup, acc, accN * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
         mrt_frame_stats pass{};
         if (runPass(r, dBitmap, dPacked, st, smp, 1, &pass)) {
@@ -1180,9 +1266,9 @@ void renderProgressiveSample(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked
             return;
         }
         if (acc != nullptr) MRT_HIP(hipMemcpyAsync(acc, r->dBackup, accN * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        allocQueues(r, std::max(1, r->chunkSlots / 2), 2);
+        MRT_HIP(hipStreamSynchronize(st));
+        planAfterOverflow(r, retry);
     }
-    throw std::runtime_error("wavefront queue overflow persists after shrinking the chunk");
 }
 
 // Renderer::renderFrame (Renderer.cpp:53-88): samples 0..spp-1 averaged with incrementalAvg.
@@ -1197,18 +1283,20 @@ void renderFrameSingle(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipS
     // (a device group's head is its shard 0 too: the group keeps getSample() itself)
     const bool groupHead = !r->peers.empty();
     if (!groupHead) r->sample.store(0);
+    r->replansFrame = 0;
     if (r->stopFlag.load()) return;  // stopRender zeroes samplesPixel_ (Renderer.cpp:97)
     const int spp = std::max(1, r->cfg.samplesPixel);
     const size_t npx = static_cast<size_t>(r->cfg.width) * static_cast<size_t>(r->cfg.height);
     mrt_frame_stats fs{};
     if (r->cfg.progressive == 0) {
-        bool done = false;
-        for (int attempt = 0; attempt < 4 && !done; ++attempt) {
+        // An overflowed pass is redone with queues planned from what it asked for (same results): at
+        // most kPlanDemandRetries such plans, then the worst-case plan, which cannot overflow
+        // (planAfterOverflow throws if it did).
+        for (int retry = 0;; ++retry) {
             fs = mrt_frame_stats{};
-            done = runPass(r, dBitmap, dPacked, st, 0, spp, &fs);
-            if (!done) allocQueues(r, std::max(1, r->chunkSlots / 2), 2);  // same results, more passes
+            if (runPass(r, dBitmap, dPacked, st, 0, spp, &fs)) break;
+            planAfterOverflow(r, retry);
         }
-        if (!done) throw std::runtime_error("wavefront queue overflow persists after shrinking the chunk");
         if (hostBitmap != nullptr && dBitmap != nullptr) {
             MRT_HIP(hipMemcpyAsync(hostBitmap, dBitmap, npx * sizeof(int32_t), hipMemcpyDeviceToHost, st));
             MRT_HIP(hipStreamSynchronize(st));
@@ -1310,6 +1398,7 @@ void renderGroupFrame(mrt_renderer* r, int32_t* dBitmap, hipStream_t st, int32_t
         toHost();
         if (!r->stopFlag.load()) r->sample.store(r->cfg.samplesPixel);
     } else {
+        for (int i = 0; i < n; ++i) shardOf(r, i)->replansFrame = 0;
         for (int smp = 0; smp < spp && !r->stopFlag.load(); ++smp) {
             forEachShard(r, [&](mrt_renderer* p, int i) {
                 renderProgressiveSample(p, nullptr, p->dOwnPacked, p->stream, smp, &shardStats[static_cast<size_t>(i)]);
@@ -1354,10 +1443,14 @@ struct MemScene {
 
 mrt_renderer* createGroup(const mrt_config* cfg, const MemScene* mem);
 
+// createGroup -> createRenderer: how many of the group's shards share this shard's GPU
+thread_local int gDeviceShare = 1;
+
 mrt_renderer* createRenderer(const mrt_config* cfg, const MemScene* mem = nullptr) {
     using namespace mrt;
     if (cfg->deviceCount > 1) return createGroup(cfg, mem);
     auto r = std::make_unique<mrt_renderer>();
+    r->deviceShare = gDeviceShare;
     r->keepHost = mem != nullptr;
     r->cfg = *cfg;
     r->objPath = cfg->objFilePath ? cfg->objFilePath : "";
@@ -1415,7 +1508,7 @@ mrt_renderer* createRenderer(const mrt_config* cfg, const MemScene* mem = nullpt
     uploadScene(r.get(), sc);
     createShadowStream(r.get());
     buildUnits(r.get());
-    allocQueues(r.get(), chunkFor(r.get()), 2);
+    planFirst(r.get());
     const size_t npx = static_cast<size_t>(r->cfg.width) * static_cast<size_t>(r->cfg.height);
     r->dBitmap = r->frameMem.alloc<int32_t>(npx);
     MRT_HIP(hipMemsetAsync(r->dBitmap, 0, sizeof(int32_t) * npx, r->stream));
@@ -1449,6 +1542,7 @@ mrt_renderer* createGroup(const mrt_config* cfg, const MemScene* mem) {
                 c.device = cfg->devices[i];
                 c.rankIndex = i;
                 c.rankCount = n;
+                gDeviceShare = static_cast<int>(std::count(cfg->devices, cfg->devices + n, cfg->devices[i]));
                 shards[static_cast<size_t>(i)].reset(createRenderer(&c, mem));
                 mrt_renderer* p = shards[static_cast<size_t>(i)].get();
                 p->dOwnPacked = p->frameMem.alloc<int32_t>(static_cast<size_t>(std::max(1, p->nSlots)));
@@ -1803,6 +1897,22 @@ static int setTuningOne(mrt_renderer* r, int32_t key, int32_t value) {
         r->shadowGridPct = value;
         return 0;
     }
+    // the queue plan's knobs: the queues are planned and allocated anew before the next pass
+    if (key == 37 && value >= 0 && value <= (1 << 20)) {
+        r->queueBudgetMiB = value;
+        r->planStale = true;
+        return 0;
+    }
+    if (key == 38 && value >= 1 && value <= 100000) {
+        r->queueGrowthPct = value;
+        r->planStale = true;
+        return 0;
+    }
+    if (key == 39 && value >= 0 && value <= (1 << 24)) {
+        r->queueSlack = value;
+        r->planStale = true;
+        return 0;
+    }
     gLastError = "unknown tuning key/value";
     return -1;
 }
@@ -1981,6 +2091,9 @@ int mrt_get_tuning(const mrt_renderer* r, int32_t key, int32_t* value) {
         case 34: *value = r->resolveAcc; return 0;
         case 35: *value = r->shadeWaitsShadow; return 0;
         case 28: *value = r->walkGridCap; return 0;
+        case 37: *value = r->queueBudgetMiB; return 0;
+        case 38: *value = r->queueGrowthPct; return 0;
+        case 39: *value = r->queueSlack; return 0;
         default: break;
     }
     gLastError = "unknown tuning key";
@@ -1989,6 +2102,50 @@ int mrt_get_tuning(const mrt_renderer* r, int32_t key, int32_t* value) {
 
 int mrt_get_frame_stats(const mrt_renderer* r, mrt_frame_stats* s) {
     *s = r->last;
+    return 0;
+}
+
+int mrt_get_queue_info(const mrt_renderer* r, mrt_queue_info* out, size_t size) {
+    using namespace mrt;
+    if (r == nullptr || out == nullptr) {
+        gLastError = "mrt_get_queue_info: null argument";
+        return -1;
+    }
+    mrt_queue_info q{};
+    q.chunkSlots = r->plan.chunkSlots;
+    q.passes = (std::max(1, r->nSlots) + q.chunkSlots - 1) / std::max<int64_t>(1, q.chunkSlots);
+    q.queueBytes = r->plan.bytes;
+    q.budgetBytes = r->planBudget;
+    q.replans = r->replans;
+    q.replansLastFrame = r->replansFrame;
+    q.worstCase = r->plan.worstCase;
+    for (int l = 0; l < kMaxLevels && l < MRT_QUEUE_LEVELS; ++l) {
+        q.rayCap[l] = l < r->nLevels ? r->plan.segCap[l] * kQueueSegs : 0;
+        q.shadowCap[l] = l < r->nLevels ? r->plan.shadowSegCap[l] * kQueueSegs : 0;
+        q.requestedRays[l] = r->reqRays[l];
+        q.requestedShadows[l] = r->reqShadows[l];
+    }
+    // a device group: the head's plan; the queue bytes and the replans of every shard
+    for (const auto& p : r->peers) {
+        q.queueBytes += p->plan.bytes;
+        q.replans += p->replans;
+        q.replansLastFrame += p->replansFrame;
+        q.worstCase = std::max<int64_t>(q.worstCase, p->plan.worstCase);
+    }
+    std::memcpy(out, &q, std::min(size, sizeof(q)));
+    return 0;
+}
+
+int mrt_plan_queues(const mrt_queue_plan_request* request, mrt_queue_plan* plan) {
+    if (request == nullptr || plan == nullptr) {
+        gLastError = "mrt_plan_queues: null argument";
+        return -1;
+    }
+    std::string err;
+    if (!mrt::planQueues(*request, plan, &err)) {
+        gLastError = err;
+        return -1;
+    }
     return 0;
 }
 

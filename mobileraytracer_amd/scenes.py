@@ -3,6 +3,8 @@
 * ``cornell_water()`` / ``teapot()`` — the OBJ/MTL/CAM fixtures of the reference's own
   instrumentation tests (``app/src/androidTest/resources``), copied as data into
   ``tests/golden``.
+* ``glass_boxes()`` — a hand-made fixture in ``tests/golden/glassboxes``: nested glass cubes whose
+  every hit spawns three rays (the queue-plan tests).
 * ``conference()`` — the benchmark scene.  ``WavefrontOBJs/conference/conference.obj`` is not
   in the reference snapshot (``.MISSING_LARGE_BLOBS:1``), so unless a real file is supplied
   (``MOBILERT_CONFERENCE_OBJ``) a stand-in is generated: a conference room built from the
@@ -35,6 +37,14 @@ def cornell_water():
 def teapot():
     d = os.path.join(GOLDEN, "teapot")
     return os.path.join(d, "teapot.obj"), os.path.join(d, "teapot.mtl"), os.path.join(d, "teapot.cam")
+
+
+def glass_boxes():
+    """Three nested glass cubes around a small light, the camera inside: every hit spawns a
+    diffuse, a specular and a transmitted ray (Kd, Ks, Kt > 0), so the ray tree grows far beyond
+    twice the camera rays (Whitted: 136 casts per pixel at depth 6, PathTracer: 559)."""
+    d = os.path.join(GOLDEN, "glassboxes")
+    return os.path.join(d, "glassboxes.obj"), os.path.join(d, "glassboxes.mtl"), os.path.join(d, "glassboxes.cam")
 
 
 # ---------------------------------------------------------------------------------------------
