@@ -11,6 +11,8 @@
  *   mrt_render_frame          Renderer::renderFrame(int32_t *bitmap, int32_t numThreads)
  *                             (app/MobileRT/Renderer.hpp:57, Renderer.cpp:53-88)
  *   mrt_render_frame_device   the same, bitmap resident in device memory (no PCIe in the window)
+ *   mrt_render_views[_device] a loop of Renderer::renderFrame over several cameras of one scene,
+ *                             as one submission (no single reference call)
  *   mrt_stop_render           Renderer::stopRender (Renderer.cpp:93-99); JNI rtStopRender
  *   mrt_get_sample            Renderer::getSample (Renderer.cpp:177-179); JNI rtGetSample
  *   mrt_get_total_casted_rays Renderer::getTotalCastedRays (Renderer.cpp:204-207)
@@ -269,6 +271,30 @@ int mrt_set_camera(mrt_renderer *r, int32_t kind, const float *position, const f
                    float a, float b);
 int mrt_set_pixel_sampler(mrt_renderer *r, int32_t kind, float value);
 int mrt_set_max_point(mrt_renderer *r, const float *maxPoint);
+/* A batch of views of the loaded scene in one submission (a turntable, a camera path, thumbnails
+ * for several clients): the wavefront runs once over nViews x pixelSlots slots instead of once per
+ * view, so the fixed cost of a level is paid once per batch.  View v's bitmap holds, bit for bit,
+ * what mrt_set_camera(views[v]) followed by mrt_render_frame[_device] writes into the same initial
+ * bitmap (any shader, accelerator, sampler, samples, depth, progressive mode and tuning); the
+ * renderer's own camera is unchanged.  mrt_get_total_casted_rays grows by, and
+ * mrt_get_frame_stats reports, the sums over the views; mrt_get_sample and mrt_stop_render act as
+ * for a frame (progressive: one pass per sample over the whole batch).  A rank shard renders its
+ * own pixel units of every view.  A device group (deviceCount > 1) is refused: -1, nothing done.
+ * Argument errors (a NULL handle or views, nViews <= 0, a camera kind outside 0 / 1, a non-finite
+ * field, both outputs NULL, nViews x pixelSlots beyond a positive int) return -1 before any device
+ * work; the views and the outputs are checked before the renderer is read. */
+typedef struct mrt_view {      /* the arguments of mrt_set_camera */
+    int32_t kind;              /* 0 Perspective, 1 Orthographic */
+    float position[3], lookAt[3], up[3];
+    float a, b;                /* hFov, vFov in degrees / sizeH, sizeV */
+} mrt_view;
+/* bitmaps: nViews x (width*height) host int32, view-major, updated in place */
+int mrt_render_views(mrt_renderer *r, const mrt_view *views, int32_t nViews, int32_t *bitmaps);
+/* d_bitmaps: device, nViews x (width*height), or NULL; d_packed: device, nViews x pixelSlots
+ * (view v's slots at v * pixelSlots, this shard's slot order), or NULL; stream as in
+ * mrt_render_frame_device */
+int mrt_render_views_device(mrt_renderer *r, const mrt_view *views, int32_t nViews,
+                            int32_t *d_bitmaps, int32_t *d_packed, void *stream);
 /* tuning knobs for A/B measurement (results are identical for every value):
  * key 1 = trace walk: 0 per-wave 64-ray batches with the plain DFS of BVH.hpp:327-384,
  *         1 persistent while-while walk (default),

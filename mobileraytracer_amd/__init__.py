@@ -98,6 +98,34 @@ class Renderer:
             self._h, ctypes.c_void_p(d_bitmap or None), ctypes.c_void_p(d_packed or None),
             ctypes.c_void_p(stream or None)))
 
+    # -- batches of views ----------------------------------------------------------------
+    @staticmethod
+    def _views(cameras):
+        """``cameras``: a sequence of set_camera's tuples (kind, position, look_at, up, a, b)."""
+        views = (_native.MrtView * max(1, len(cameras)))()
+        for v, (kind, position, look_at, up, a, b) in zip(views, cameras):
+            v.kind = int(kind)
+            v.position[:] = [float(x) for x in position]
+            v.lookAt[:] = [float(x) for x in look_at]
+            v.up[:] = [float(x) for x in up]
+            v.a, v.b = float(a), float(b)
+        return views
+
+    def render_views(self, cameras, bitmaps: np.ndarray) -> None:
+        """mrt_render_views: one frame per camera in one submission, view v into ``bitmaps[v]`` (C-contiguous
+        int32 of shape (K, width*height)), bit-equal to set_camera + render_frame per view; the
+        renderer's own camera is unchanged."""
+        assert bitmaps.dtype == np.int32 and bitmaps.flags["C_CONTIGUOUS"]
+        assert bitmaps.shape == (len(cameras), self.config.width * self.config.height)
+        _native.check(self._lib.mrt_render_views(self._h, self._views(cameras), len(cameras), _ptr(bitmaps)))
+
+    def render_views_device(self, cameras, d_bitmaps: int = 0, d_packed: int = 0, stream: int = 0) -> None:
+        """mrt_render_views_device: the batch into device memory (pointers as ints, e.g. a torch int32
+        tensor's ``data_ptr()``): ``d_bitmaps`` K x (width*height), ``d_packed`` K x pixelSlots."""
+        _native.check(self._lib.mrt_render_views_device(
+            self._h, self._views(cameras), len(cameras), ctypes.c_void_p(d_bitmaps or None),
+            ctypes.c_void_p(d_packed or None), ctypes.c_void_p(stream or None)))
+
     def unpack_gathered(self, d_gathered: int, d_bitmap: int, stream: int = 0) -> None:
         _native.check(self._lib.mrt_unpack_gathered(self._h, ctypes.c_void_p(d_gathered),
                                                      ctypes.c_void_p(d_bitmap), ctypes.c_void_p(stream or None)))

@@ -25,7 +25,7 @@ EXPORTED_SYMBOLS = (
     "mrt_android_stop_render", "mrt_android_finish_render", "mrt_android_state", "mrt_android_fps",
     "mrt_android_time_renderer", "mrt_android_sample", "mrt_android_number_of_lights", "mrt_android_resize",
     "mrt_android_vertices", "mrt_android_colors", "mrt_android_camera", "mrt_android_reset",
-    "mrt_get_queue_info", "mrt_plan_queues",
+    "mrt_get_queue_info", "mrt_plan_queues", "mrt_render_views", "mrt_render_views_device",
     "RayTrace", "stopRender",
 )
 
@@ -51,6 +51,11 @@ class MrtAndroidConfig(ctypes.Structure):  # include/mobilert_android.h
 
 class MrtBlob(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("bytes", ctypes.c_char_p), ("size", ctypes.c_int64)]
+
+
+class MrtView(ctypes.Structure):  # mrt_view: the arguments of mrt_set_camera
+    _fields_ = [("kind", ctypes.c_int32), ("position", ctypes.c_float * 3), ("lookAt", ctypes.c_float * 3),
+                ("up", ctypes.c_float * 3), ("a", ctypes.c_float), ("b", ctypes.c_float)]
 
 
 class MrtSceneInfo(ctypes.Structure):
@@ -138,6 +143,8 @@ def load_library(path=LIB_PATH):
         "mrt_destroy": (None, [vp]),
         "mrt_render_frame": (ctypes.c_int, [vp, vp]),
         "mrt_render_frame_device": (ctypes.c_int, [vp, vp, vp, vp]),
+        "mrt_render_views": (ctypes.c_int, [vp, P(MrtView), ctypes.c_int32, vp]),
+        "mrt_render_views_device": (ctypes.c_int, [vp, P(MrtView), ctypes.c_int32, vp, vp, vp]),
         "mrt_unpack_gathered": (ctypes.c_int, [vp, vp, vp, vp]),
         "mrt_stop_render": (ctypes.c_int, [vp]),
         "mrt_get_sample": (ctypes.c_int32, [vp]),

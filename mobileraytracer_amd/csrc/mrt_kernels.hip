@@ -103,31 +103,9 @@ __device__ __forceinline__ void slotToXY(const PixelMap& m, int slot, int* x, in
 }
 // rect.z = unit width (columns), rect.w = unit height (rows)
 
-// Camera ray of path p (Renderer.cpp:108-111, 131-140 with Perspective / Orthographic::generateRay):
-// origin (w = path key bits), direction (w = kNoPrim: no source primitive).
-__device__ __forceinline__ void cameraRay(const RaygenArgs& a, int p, float4* o4, float4* d4) {
-    const int slot = a.slotBase + p / a.spp;
-    const int s = p % a.spp;
-    int x, y;
-    slotToXY(a.map, slot, &x, &y);
-    const uint32_t pixelIndex = static_cast<uint32_t>(y * a.width + x);
-    const uint32_t key = pathKey(pixelIndex, static_cast<uint32_t>(a.sampleBase + s));
-    // Renderer.cpp:108-111, 131-140
-    const float invW = 1.0F / static_cast<float>(a.width);
-    const float invH = 1.0F / static_cast<float>(a.height);
-    const float pixW = 0.5F / static_cast<float>(a.width);
-    const float pixH = 0.5F / static_cast<float>(a.height);
-    const float u = static_cast<float>(x) * invW;
-    const float v = static_cast<float>(y) * invH;
-    float r1 = a.constJitter, r2 = a.constJitter;  // Constant(value) (Constant.cpp:9-11)
-    if (a.tableJitter != 0) {  // StaticHaltonSeq: the two draws of the pixel sampler, one 8-byte read
-        const float2 j = a.jitter[sampleBlock(key, 0u)];
-        r1 = j.x;
-        r2 = j.y;
-    }
-    const float devU = (r1 - 0.5F) * 2.0F * pixW;
-    const float devV = (r2 - 0.5F) * 2.0F * pixH;
-    const GCamera& c = a.cam;
+// Perspective / Orthographic::generateRay of camera c for the pixel at (u, v), jittered by (devU, devV)
+__device__ __forceinline__ void cameraRayOf(const GCamera& c, float u, float v, float devU, float devV, uint32_t key,
+                                            float4* o4, float4* d4) {
     v3 origin, dir;
     if (c.kind == 1) {  // Orthographic.cpp:15-24 (hFov / vFov hold the half sizes)
         const float rf = (u - 0.5F) * c.hFov;
@@ -148,13 +126,73 @@ __device__ __forceinline__ void cameraRay(const RaygenArgs& a, int p, float4* o4
     *o4 = make_float4(origin.x, origin.y, origin.z, bitsf(key));
     *d4 = make_float4(dir.x, dir.y, dir.z, bitsf(kNoPrim));
 }
+// Camera ray of path p (Renderer.cpp:108-111, 131-140 with Perspective / Orthographic::generateRay):
+// origin (w = path key bits), direction (w = kNoPrim: no source primitive).
+// kViews (a batch of views, mrt_render_views): slotBase + p / spp is a virtual slot, view *
+// viewSlots + slot, and the camera is a.cams[view].  The pixel, the path key and with it every
+// sampler draw are the single view's: only the camera differs, and nothing below level 1 knows it.
+// A wave's 64 consecutive paths normally lie in one view: its camera is then wave-uniform and is
+// read once per wave through the scalar cache into SGPRs (the packet walk's idiom,
+// mrt_trace_packet.hpp), as the single view's comes from the kernel arguments.  A wave that
+// straddles a view boundary (viewSlots * spp no multiple of 64, or a chunk cut inside a view) reads
+// each lane's camera with vector loads; its lanes may then hold cameras of both kinds.
+static_assert(sizeof(GCamera) == 64, "cameraRay reads a view's camera as 16 dwords");
+template <bool kViews = false>
+__device__ __forceinline__ void cameraRay(const RaygenArgs& a, int p, float4* o4, float4* d4) {
+    int slot = a.slotBase + p / a.spp;
+    int view = 0;
+    if constexpr (kViews) {
+        view = slot / a.viewSlots;
+        slot -= view * a.viewSlots;
+    }
+    const int s = p % a.spp;
+    int x, y;
+    slotToXY(a.map, slot, &x, &y);
+    const uint32_t pixelIndex = static_cast<uint32_t>(y * a.width + x);
+    const uint32_t key = pathKey(pixelIndex, static_cast<uint32_t>(a.sampleBase + s));
+    // Renderer.cpp:108-111, 131-140
+    const float invW = 1.0F / static_cast<float>(a.width);
+    const float invH = 1.0F / static_cast<float>(a.height);
+    const float pixW = 0.5F / static_cast<float>(a.width);
+    const float pixH = 0.5F / static_cast<float>(a.height);
+    const float u = static_cast<float>(x) * invW;
+    const float v = static_cast<float>(y) * invH;
+    float r1 = a.constJitter, r2 = a.constJitter;  // Constant(value) (Constant.cpp:9-11)
+    if (a.tableJitter != 0) {  // StaticHaltonSeq: the two draws of the pixel sampler, one 8-byte read
+        const float2 j = a.jitter[sampleBlock(key, 0u)];
+        r1 = j.x;
+        r2 = j.y;
+    }
+    const float devU = (r1 - 0.5F) * 2.0F * pixW;
+    const float devV = (r2 - 0.5F) * 2.0F * pixH;
+    if constexpr (kViews) {
+        const int first = __builtin_amdgcn_readfirstlane(view);
+        if (__ballot(view != first) == 0) {  // one view in the wave: its camera in SGPRs
+            ConstU32* const w = (ConstU32*)(a.cams) + 16 * first;  // NOLINT: address-space cast
+            const float4 c0 = sload4f(w), c1 = sload4f(w + 4), c2 = sload4f(w + 8), c3 = sload4f(w + 12);
+            pinSgprs(c0);
+            pinSgprs(c1);
+            pinSgprs(c2);
+            pinSgprs(c3);
+            const GCamera c{v3{c0.x, c0.y, c0.z}, v3{c0.w, c1.x, c1.y}, v3{c1.z, c1.w, c2.x}, v3{c2.y, c2.z, c2.w},
+                            c3.x, c3.y, __float_as_int(c3.z), 0};
+            cameraRayOf(c, u, v, devU, devV, key, o4, d4);
+        } else {  // a wave across a view boundary: per-lane cameras
+            const GCamera c = a.cams[view];
+            cameraRayOf(c, u, v, devU, devV, key, o4, d4);
+        }
+    } else {
+        cameraRayOf(a.cam, u, v, devU, devV, key, o4, d4);
+    }
+}
 
+template <bool kViews>
 __global__ __launch_bounds__(256) void k_raygen(RaygenArgs a, Level lv, int* counters) {
     const int p = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
     if (p == 0) denseCounts(counters, 1, false, a.nPaths, lv.segCap);
     if (p >= a.nPaths) return;
     float4 o4, d4;
-    cameraRay(a, p, &o4, &d4);
+    cameraRay<kViews>(a, p, &o4, &d4);
     lv.rO[p] = o4;
     lv.rD[p] = d4;
     lv.tree[p] = 1u;
@@ -279,11 +317,12 @@ __global__ __launch_bounds__(kWalkThreads, MRT_WALK_WAVES) void k_trace(DScene s
 // Camera rays generated where they are walked (round 6, tuning key 33): cameraRay (k_raygen's
 // function) per lane at the start of each packet, and the records k_shade reads stored from there,
 // so that k_raygen's launch and the walk's reads of its records are gone.
+template <bool kViews>
 struct PacketRaysStore {
     const RaygenArgs* a;
     Level lv;
     __device__ __forceinline__ void operator()(int i, float4* o4, float4* d4) const {
-        cameraRay(*a, i, o4, d4);
+        cameraRay<kViews>(*a, i, o4, d4);
         if (a->storeRays != 0) {  // (else k_shade regenerates them)
             lv.rO[i] = *o4;
             lv.rD[i] = *d4;
@@ -293,10 +332,11 @@ struct PacketRaysStore {
 };
 
 // Level-1 (camera) rays in cull modes 0 and 3: the wave-coherent walk (mrt_trace_packet.hpp).
-// kGen: the walk generates the camera rays (PacketRaysStore) instead of reading k_raygen's.
+// kGen: the walk generates the camera rays (PacketRaysStore) instead of reading k_raygen's
+// (1: of the renderer's camera, 2: of a batch of views, cameraRay's kViews).
 // (7 waves per SIMD with kGen: at 8 its 64 VGPRs spilled 12 B; the packet walk measured the same
 // at 6, 7 and 8, section 3.1 of DESIGN.md)
-template <bool kCount, int kCull, bool kGen>
+template <bool kCount, int kCull, int kGen>
 __global__ __launch_bounds__(kWalkThreads, kGen ? 7 : 8) void k_trace_packet(DScene s, Level lv, int* counters, int level,
                                                                    int2* gstack, int gdepth, unsigned long long* stats,
                                                                    RaygenArgs ra) {
@@ -309,9 +349,9 @@ __global__ __launch_bounds__(kWalkThreads, kGen ? 7 : 8) void k_trace_packet(DSc
     const int count = kGen ? min(ra.nPaths, lv.cap) : segMap(counters, level, false, lv.segCap).total();
     int* fetch = counters + kCntFetchShards + level * kMaxFetchShards * kFetchStride;
     TravCount cnt{0u, 0u};
-    if constexpr (kGen)
+    if constexpr (kGen != 0)
         tracePacket<kCount, kCull>(s, lv.rO, lv.rD, lv.hit, count, fetch, st, &cnt, waveStacks[threadIdx.x / 64], NoPost(),
-                                   PacketRaysStore{&ra, lv});
+                                   PacketRaysStore<kGen == 2>{&ra, lv});
     else
         tracePacket<kCount, kCull>(s, lv.rO, lv.rD, lv.hit, count, fetch, st, &cnt, waveStacks[threadIdx.x / 64]);
     if (kCount) {
@@ -698,7 +738,8 @@ __device__ __forceinline__ v3 firstChildDir(const ShadeState& v) {
 constexpr int kShadeLdsTable = 256;  // float4: 4 per material, then 4 per light
 // kRegen (level 1, tuning key 33 = 2): the camera rays regenerated here (cameraRay on ra, the
 // function the packet walk generated them with: the same bits) instead of read from lv's records
-template <int kShader, bool kFull, bool kRegen>
+// (1: of the renderer's camera, 2: of a batch of views, cameraRay's kViews)
+template <int kShader, bool kFull, int kRegen>
 __global__ __launch_bounds__(kBlock) void k_shade(DScene s, Level lv, Level nx, int* counters, int level, ShadeArgs a,
                                                   int deadNext, RaygenArgs ra) {
     __shared__ float4 tab[kFull ? 1 : kShadeLdsTable];
@@ -731,8 +772,8 @@ __global__ __launch_bounds__(kBlock) void k_shade(DScene s, Level lv, Level nx, 
             }
             float4 o4, d4;
             uint32_t tc = 1u;
-            if constexpr (kRegen) {
-                cameraRay(ra, i, &o4, &d4);
+            if constexpr (kRegen != 0) {
+                cameraRay<kRegen == 2>(ra, i, &o4, &d4);
             } else {
                 o4 = lv.rO[i];
                 d4 = lv.rD[i];
@@ -818,15 +859,18 @@ struct PacketShade {
 
 // ... and its camera rays are generated where they are walked (cameraRay, k_raygen's function):
 // level 1's ray records are not written or read
+template <bool kViews>
 struct PacketRays {
     const RaygenArgs* a;
-    __device__ __forceinline__ void operator()(int i, float4* o4, float4* d4) const { cameraRay(*a, i, o4, d4); }
+    __device__ __forceinline__ void operator()(int i, float4* o4, float4* d4) const {
+        cameraRay<kViews>(*a, i, o4, d4);
+    }
 };
 
 #ifndef MRT_FUSED_WAVES
 #define MRT_FUSED_WAVES 6
 #endif
-template <int kShader, int kCull>
+template <int kShader, int kCull, bool kViews>
 __global__ __launch_bounds__(kWalkThreads, MRT_FUSED_WAVES) void k_trace_packet_shade(DScene s, Level lv, Level nx, int* counters,
                                                                          int level, ShadeArgs a, int deadNext,
                                                                          int2* gstack, int gdepth, RaygenArgs ra) {
@@ -839,7 +883,7 @@ __global__ __launch_bounds__(kWalkThreads, MRT_FUSED_WAVES) void k_trace_packet_
     TravCount cnt{0u, 0u};
     const PacketShade<kShader> post{&s, lv, nx, counters, level, a, deadNext != 0};
     tracePacket<false, kCull>(s, lv.rO, lv.rD, lv.hit, count, fetch, st, &cnt, waveStacks[threadIdx.x / 64], post,
-                              PacketRays{&ra});
+                              PacketRays<kViews>{&ra});
 }
 
 // Single-level shaders: the camera ray's shade() spawns no rays, so the result is final here.
@@ -1022,12 +1066,27 @@ __global__ __launch_bounds__(256) void k_resolve(DScene s, Level lv, Level nx, i
 // ---------------------------------------------------------------------------------------
 // Pixel slot a.slotBase + q: incrementalAvg (Utils.cpp:66-90) of its samples, res[q * spp + s], in
 // sample order, into the bitmap and / or the packed shard buffer.
+// kViews (a batch of views): the slot is virtual, view * viewSlots + the shard's slot; the pixel
+// goes to its view's bitmap, and to the packed buffer at the virtual slot (accumIndex).
+template <bool kViews>
+__device__ __forceinline__ auto accumIndex(const AccumArgs& a, int slot) {
+    int view = 0;
+    if constexpr (kViews) {
+        view = slot / a.viewSlots;
+        slot -= view * a.viewSlots;
+    }
+    int x, y;
+    slotToXY(a.map, slot, &x, &y);
+    if constexpr (kViews)
+        return static_cast<size_t>(view) * static_cast<size_t>(a.viewPixels) + static_cast<size_t>(y * a.width + x);
+    else
+        return y * a.width + x;
+}
+template <bool kViews>
 __device__ __forceinline__ void accumulatePixel(const AccumArgs& a, const float4* res, int32_t* bitmap, int32_t* packed,
                                                 int q) {
     const int slot = a.slotBase + q;
-    int x, y;
-    slotToXY(a.map, slot, &x, &y);
-    const int idx = y * a.width + x;
+    const auto idx = accumIndex<kViews>(a, slot);
     int32_t c = 0;  // the running average (progressive passes: sampleBase > 0)
     if (a.sampleBase > 0) c = bitmap != nullptr ? bitmap[idx] : (packed != nullptr ? packed[slot] : 0);
     for (int s = 0; s < a.spp; ++s) {
@@ -1038,10 +1097,11 @@ __device__ __forceinline__ void accumulatePixel(const AccumArgs& a, const float4
     if (packed != nullptr) packed[slot] = c;
 }
 
+template <bool kViews>
 __global__ __launch_bounds__(256) void k_accumulate(AccumArgs a, const float4* res, int32_t* bitmap, int32_t* packed) {
     const int q = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
     if (q >= a.nSlots) return;
-    accumulatePixel(a, res, bitmap, packed, q);
+    accumulatePixel<kViews>(a, res, bitmap, packed, q);
 }
 
 // scatter a gathered, rank-packed buffer into the bitmap (multi-GPU frame assembly)
@@ -1208,7 +1268,10 @@ void launchLoadRays(const Level& lv, const float* orig, const float* dir, const 
 // launch wrappers
 void launchRaygen(const RaygenArgs& a, const Level& lv, int* counters, hipStream_t st) {
     const int blocks = (a.nPaths + 255) / 256;
-    hipLaunchKernelGGL(k_raygen, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, a, lv, counters);
+    if (a.cams != nullptr)
+        hipLaunchKernelGGL(k_raygen<true>, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, a, lv, counters);
+    else
+        hipLaunchKernelGGL(k_raygen<false>, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, a, lv, counters);
 }
 
 // Persistent grid: the kernel's own occupancy x CUs workgroups, capped by the thread count the
@@ -1276,16 +1339,20 @@ void launchTrace(const DScene& s, const Level& lv, int* counters, int level, int
     }
     const int gridPct = 100;
     if (level == 1 && packetLevel1(s)) {
-        const int g = std::max(1, gen != nullptr ? persistentGrid(k_trace_packet<false, kCullExact, true>, 11, maxThreads)
-                                                  : persistentGrid(k_trace_packet<false, kCullExact, false>, 10, maxThreads));
+        // (a batch of views: the generating walk's kViews form, occupancy slot 16)
+        const bool views = gen != nullptr && gen->cams != nullptr;
+        const int g = std::max(1, views           ? persistentGrid(k_trace_packet<false, kCullExact, 2>, 16, maxThreads)
+                                  : gen != nullptr ? persistentGrid(k_trace_packet<false, kCullExact, 1>, 11, maxThreads)
+                                                   : persistentGrid(k_trace_packet<false, kCullExact, 0>, 10, maxThreads));
         const RaygenArgs ra = gen != nullptr ? *gen : RaygenArgs{};
 #define MRT_LAUNCH_PACKET(CNT, C, GEN)                                                                        \
         hipLaunchKernelGGL((k_trace_packet<CNT, C, GEN>), dim3(g), dim3(kWalkThreads), 0, st, s, lv, counters, level, \
                            gstack, gdepth, stats, ra)
 #define MRT_LAUNCH_PACKET_GEN(CNT, C)                     \
         do {                                              \
-            if (gen != nullptr) MRT_LAUNCH_PACKET(CNT, C, true); \
-            else MRT_LAUNCH_PACKET(CNT, C, false);        \
+            if (views) MRT_LAUNCH_PACKET(CNT, C, 2);      \
+            else if (gen != nullptr) MRT_LAUNCH_PACKET(CNT, C, 1); \
+            else MRT_LAUNCH_PACKET(CNT, C, 0);            \
         } while (0)
         if (s.cull == kCullExact) {
             if (countStats) MRT_LAUNCH_PACKET_GEN(true, kCullExact);
@@ -1320,12 +1387,19 @@ void launchTraceShadeFused(int shader, const DScene& s, const Level& lv, const L
                            const ShadeArgs& a, int2* gstack, int gdepth, int maxThreads, hipStream_t st, bool deadNext,
                            const RaygenArgs& ra) {
     const int dead = deadNext ? 1 : 0;
-#define MRT_LAUNCH_FUSED(SH, C)                                                                                  \
+    // (a batch of views, ra.cams: the kViews form, occupancy slots 17-20)
+#define MRT_LAUNCH_FUSED_ONE(SH, C, VIEWS)                                                                       \
     do {                                                                                                         \
-        const int g = std::max(1, persistentGrid(k_trace_packet_shade<SH, C>, 12 + (SH == kShaderWhitted ? 0 : 1) + \
-                                                 (C == kCullExact ? 0 : 2), maxThreads));                         \
-        hipLaunchKernelGGL((k_trace_packet_shade<SH, C>), dim3(g), dim3(kWalkThreads), 0, st, s, lv, nx, counters,  \
-                           level, a, dead, gstack, gdepth, ra);                                                 \
+        const int g = std::max(1, persistentGrid(k_trace_packet_shade<SH, C, VIEWS>, (VIEWS ? 17 : 12) +         \
+                                                 (SH == kShaderWhitted ? 0 : 1) + (C == kCullExact ? 0 : 2),      \
+                                                 maxThreads));                                                   \
+        hipLaunchKernelGGL((k_trace_packet_shade<SH, C, VIEWS>), dim3(g), dim3(kWalkThreads), 0, st, s, lv, nx,  \
+                           counters, level, a, dead, gstack, gdepth, ra);                                        \
+    } while (0)
+#define MRT_LAUNCH_FUSED(SH, C)                            \
+    do {                                                   \
+        if (ra.cams != nullptr) MRT_LAUNCH_FUSED_ONE(SH, C, true); \
+        else MRT_LAUNCH_FUSED_ONE(SH, C, false);           \
     } while (0)
     if (shader == kShaderPathTracer) {
         if (s.cull == kCullExact) MRT_LAUNCH_FUSED(kShaderPathTracer, kCullExact);
@@ -1335,6 +1409,7 @@ void launchTraceShadeFused(int shader, const DScene& s, const Level& lv, const L
         else MRT_LAUNCH_FUSED(kShaderWhitted, kCullNone);
     }
 #undef MRT_LAUNCH_FUSED
+#undef MRT_LAUNCH_FUSED_ONE
 }
 
 void launchShade(int shader, const DScene& s, const Level& lv, const Level& nx, int* counters, int level,
@@ -1347,8 +1422,9 @@ void launchShade(int shader, const DScene& s, const Level& lv, const Level& nx, 
                        dead, ra)
 #define MRT_LAUNCH_SHADE(SH, FULL)                         \
     do {                                                   \
-        if (regen != nullptr) MRT_LAUNCH_SHADE_ONE(SH, FULL, true); \
-        else MRT_LAUNCH_SHADE_ONE(SH, FULL, false);        \
+        if (regen != nullptr && regen->cams != nullptr) MRT_LAUNCH_SHADE_ONE(SH, FULL, 2); \
+        else if (regen != nullptr) MRT_LAUNCH_SHADE_ONE(SH, FULL, 1); \
+        else MRT_LAUNCH_SHADE_ONE(SH, FULL, 0);            \
     } while (0)
     const bool full = s.textured != 0 || a.stats != nullptr || s.leanShade == 0 ||
                       4 * (s.nMats + s.nLights) > kShadeLdsTable;
@@ -1403,7 +1479,7 @@ void launchResolve(int shader, const DScene& s, const Level& lv, const Level& nx
 // records are never written or re-read.  The same resolveValue and incrementalAvg on the same
 // inputs: the same bits.  (A thread per slot resolving its samples one after another measured
 // slower, C4 13.65 -> 13.78 ms: four dependent gather chains per thread.)
-template <int kShader, bool kTex>
+template <int kShader, bool kTex, bool kViews>
 __global__ __launch_bounds__(256) void k_resolve_accumulate(DScene s, Level lv, Level nx, ShadeArgs sa, int deadChildren,
                                                             AccumArgs a, int32_t* bitmap, int32_t* packed) {
     const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
@@ -1418,18 +1494,14 @@ __global__ __launch_bounds__(256) void k_resolve_accumulate(DScene s, Level lv, 
         if (k == 0 && i < n) {
             if (j == 0 && a.sampleBase > 0) {  // the running average (progressive passes)
                 const int slot = a.slotBase + i / a.spp;
-                int px, py;
-                slotToXY(a.map, slot, &px, &py);
-                c = bitmap != nullptr ? bitmap[py * a.width + px] : (packed != nullptr ? packed[slot] : 0);
+                c = bitmap != nullptr ? bitmap[accumIndex<kViews>(a, slot)] : (packed != nullptr ? packed[slot] : 0);
             }
             c = incrementalAvg(v3{x, y, z}, c, a.sampleBase + j + 1);
         }
     }
     if (k == 0 && i < n) {
         const int slot = a.slotBase + i / a.spp;
-        int px, py;
-        slotToXY(a.map, slot, &px, &py);
-        if (bitmap != nullptr) bitmap[py * a.width + px] = c;
+        if (bitmap != nullptr) bitmap[accumIndex<kViews>(a, slot)] = c;
         if (packed != nullptr) packed[slot] = c;
     }
 }
@@ -1439,9 +1511,14 @@ bool launchResolveAccumulate(int shader, const DScene& s, const Level& lv, const
     if (a.spp <= 0 || 64 % a.spp != 0) return false;  // a slot's samples must share a wave
     const int dead = deadChildren ? 1 : 0;
     const int blocks = std::max(1, (a.nSlots * a.spp + 255) / 256);
-#define MRT_LAUNCH_RA(SH, TEX)                                                                                  \
-    hipLaunchKernelGGL((k_resolve_accumulate<SH, TEX>), dim3(blocks), dim3(256), 0, st, s, lv, nx, sa, dead, a, \
-                       bitmap, packed)
+#define MRT_LAUNCH_RA_ONE(SH, TEX, VIEWS)                                                                       \
+    hipLaunchKernelGGL((k_resolve_accumulate<SH, TEX, VIEWS>), dim3(blocks), dim3(256), 0, st, s, lv, nx, sa, dead, \
+                       a, bitmap, packed)
+#define MRT_LAUNCH_RA(SH, TEX)                               \
+    do {                                                     \
+        if (a.viewSlots > 0) MRT_LAUNCH_RA_ONE(SH, TEX, true); \
+        else MRT_LAUNCH_RA_ONE(SH, TEX, false);              \
+    } while (0)
     const bool tex = s.textured != 0;
     if (shader == kShaderPathTracer) {
         if (tex) MRT_LAUNCH_RA(kShaderPathTracer, true);
@@ -1453,12 +1530,16 @@ bool launchResolveAccumulate(int shader, const DScene& s, const Level& lv, const
         return false;
     }
 #undef MRT_LAUNCH_RA
+#undef MRT_LAUNCH_RA_ONE
     return true;
 }
 
 void launchAccumulate(const AccumArgs& a, const float4* res, int32_t* bitmap, int32_t* packed, hipStream_t st) {
     const int blocks = (a.nSlots + 255) / 256;
-    hipLaunchKernelGGL(k_accumulate, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, a, res, bitmap, packed);
+    if (a.viewSlots > 0)
+        hipLaunchKernelGGL(k_accumulate<true>, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, a, res, bitmap, packed);
+    else
+        hipLaunchKernelGGL(k_accumulate<false>, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, a, res, bitmap, packed);
 }
 
 void launchUnpackRanks(const UnpackArgs& a, int ranks, int maxN, const int32_t* gathered, int32_t* bitmap,
@@ -1492,8 +1573,8 @@ int traceResidentThreadsPerCU() {
                              reinterpret_cast<const void*>(k_shadow<false, 1, kCullCertified>),
                              reinterpret_cast<const void*>(k_shadow<false, 1, kCullNone>),
                              reinterpret_cast<const void*>(k_shadow<false, 1, kCullExact>),
-                             reinterpret_cast<const void*>(k_trace_packet<false, kCullExact, false>),
-                             reinterpret_cast<const void*>(k_trace_packet<false, kCullNone, false>)};
+                             reinterpret_cast<const void*>(k_trace_packet<false, kCullExact, 0>),
+                             reinterpret_cast<const void*>(k_trace_packet<false, kCullNone, 0>)};
     for (const void* k : kernels) {
         int n = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, kWalkThreads, 0) == hipSuccess)

@@ -142,7 +142,11 @@ struct RaygenArgs {
     // the level-1 packet walk generating these rays (tuning key 33): 1 also stores their records,
     // 0 leaves them to k_shade to regenerate
     int storeRays;
-    int pad;
+    // A batch of views (mrt_render_views): the chunk's slots are virtual slots, view * viewSlots +
+    // slot of the shard, and a path's camera is cams[view] (device memory) instead of cam.  Null for
+    // a plain frame, whose kernels are instantiations of their own and never read these two.
+    int viewSlots;
+    const GCamera* cams;
 };
 
 struct ShadeArgs {
@@ -194,9 +198,11 @@ struct AccumArgs {
     int nSlots;
     int spp;
     int sampleBase;
-    int pad;
+    // a batch of views (viewSlots > 0): slotBase + q is a virtual slot, view * viewSlots + slot; view
+    // v's bitmap starts at v * viewPixels, the packed buffer is indexed by the virtual slot
+    int viewSlots;
+    int viewPixels;
 };
-
 
 
 void launchRaygen(const RaygenArgs& a, const Level& lv, int* counters, hipStream_t st);

@@ -375,6 +375,17 @@ struct mrt_renderer {
     int32_t* dBitmap = nullptr;  // for the host-bitmap entry point
     int32_t* dBackup = nullptr;  // progressive mode: the running average before the current pass
     size_t backupN = 0;
+    // A batch of views (mrt_render_views): while it renders, the passes run over views * nSlots
+    // virtual slots (view v's slots at v * nSlots) with the views' cameras at batchCams (in
+    // dViewCams); 1 and null otherwise (a batch of one view is a frame with that view's camera).
+    int views = 1;
+    const mrt::GCamera* batchCams = nullptr;
+    mrt::GCamera* dViewCams = nullptr;
+    size_t viewCamsN = 0;
+    std::vector<mrt::GCamera> hostViewCams;  // the upload's source
+    int32_t* dViewBitmaps = nullptr;         // the host entry point's staging: views x width x height
+    size_t viewBitmapsN = 0;
+    int64_t planSlots = 0;                   // the (virtual) slot count the queue plan was made for
     hipStream_t stream = nullptr;
     int overlap = 1;                     // tuning key 3: shadow rays on their own stream
     int skipLast = 1;                    // tuning key 7: no closest-hit walk for the depth-capped last level
@@ -847,6 +858,9 @@ void createShadowStream(mrt_renderer* r) {
 // within the path budget (maxPathsPerPass) and the byte budget: tuning key 37, else half of the
 // device memory free once the current queues are released.  Frees nothing: a plan that fails
 // leaves the renderer with the queues it had.
+// The slots a pass runs over: the shard's, or a batch's virtual slots (views x the shard's).
+int64_t passSlots(const mrt_renderer* r) { return static_cast<int64_t>(r->nSlots) * std::max(1, r->views); }
+
 mrt_queue_plan_request planRequest(mrt_renderer* r) {
     using namespace mrt;
     mrt_queue_plan_request q{};
@@ -858,7 +872,7 @@ mrt_queue_plan_request planRequest(mrt_renderer* r) {
     q.segments = kQueueSegs;
     q.growthPct = r->queueGrowthPct;
     q.slack = r->queueSlack;
-    q.pixelSlots = std::max(1, r->nSlots);
+    q.pixelSlots = std::max<int64_t>(1, passSlots(r));  // (a batch: one chunk holds as many views as fit)
     q.pathBudget = r->cfg.maxPathsPerPass > 0 ? r->cfg.maxPathsPerPass : kPlanPathBudget;
     if (r->queueBudgetMiB > 0) {
         q.byteBudget = static_cast<int64_t>(r->queueBudgetMiB) << 20;
@@ -886,6 +900,7 @@ void adoptPlan(mrt_renderer* r, mrt_queue_plan_request q) {
     }
     r->plan = plan;
     r->planBudget = q.byteBudget;
+    r->planSlots = q.pixelSlots;
     r->planStale = false;
     allocQueues(r);
 }
@@ -973,8 +988,14 @@ void renderPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t
     // every material is finite (Ks * 0 and Kd * 0 added to sums that start at +0), and the
     // parents write no payload for them (only their count)
     const bool skipLastShade = skipLast && nLevels >= 2 && r->ds.matsFinite != 0;
-    for (int slot0 = 0; slot0 < r->nSlots && !r->stopFlag.load(); slot0 += r->chunkSlots) {
-        const int nChunk = std::min(r->chunkSlots, r->nSlots - slot0);
+    // A batch of views is one longer slot range: virtual slot vs is slot vs % nSlots of view
+    // vs / nSlots, so a chunk may begin and end inside a view and span several.  Only level 1 (ray
+    // generation, the accumulation) maps a slot to its view; pathsPerLane and what follows from it
+    // see the batch's size.
+    const int64_t nTotal = passSlots(r);
+    for (int64_t slot64 = 0; slot64 < nTotal && !r->stopFlag.load(); slot64 += r->chunkSlots) {
+        const int slot0 = static_cast<int>(slot64);
+        const int nChunk = static_cast<int>(std::min<int64_t>(r->chunkSlots, nTotal - slot64));
         if (!r->countersClean) MRT_HIP(hipMemsetAsync(pp.counters, 0, sizeof(int) * kNumCounters, st));
         r->countersClean = false;
         RaygenArgs ra{};
@@ -990,6 +1011,10 @@ void renderPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t
         ra.sppTotal = r->cfg.samplesPixel;
         setPixelSampler(r, &ra);
         ra.sampleBase = sampleBase;
+        if (r->batchCams != nullptr) {
+            ra.cams = r->batchCams;
+            ra.viewSlots = r->nSlots;
+        }
         // With few paths per resident walk lane (a small shard: C4 at N >= 4) the levels are short
         // and tail-bound, and a full-width shadow walk starves the next level's shading of CUs;
         // a narrower shadow grid leaves them room (C4 shard at N = 8: 2.92 -> 2.83 ms; at N = 1 the
@@ -1108,6 +1133,10 @@ void renderPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t
         aa.nSlots = nChunk;
         aa.spp = spp;
         aa.sampleBase = sampleBase;
+        if (r->batchCams != nullptr) {
+            aa.viewSlots = r->nSlots;
+            aa.viewPixels = r->cfg.width * r->cfg.height;
+        }
         const int topResolve = skipLastShade ? nLevels - 1 : nLevels;
         // level 1's resolve folded into the accumulation (tuning key 34): no level-1 radiance records
         const bool resolveAcc = r->resolveAcc != 0 && topResolve >= 1;
@@ -1124,7 +1153,7 @@ void renderPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t
         }
         // the statistics so far into the pinned host block, the counters reset; after the last chunk
         // the statistics too
-        const bool lastChunk = slot0 + nChunk >= r->nSlots;
+        const bool lastChunk = slot64 + nChunk >= nTotal;
         launchTally(pp.counters, nLevels, pp.stats, st, skipLast ? nLevels : 0, r->hostStats, lastChunk);
         r->countersClean = true;
         if (lastChunk) r->statsClean = true;
@@ -1136,7 +1165,9 @@ void renderPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t
 bool runPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t st, int sampleBase, int spp,
              mrt_frame_stats* fs) {
     using namespace mrt;
-    if (r->planStale) planFirst(r);  // (tuning keys 37-39 changed)
+    // (tuning keys 37-39 changed; or the slot count did, between a frame and a batch of views: the
+    // chunk is sized for the range the pass runs over, and a plan learned for the other count is dropped)
+    if (r->planStale || r->planSlots != std::max<int64_t>(1, passSlots(r))) planFirst(r);
     const auto t0 = std::chrono::steady_clock::now();
     renderPass(r, dBitmap, dPacked, st, sampleBase, spp);
     MRT_HIP(hipStreamSynchronize(st));  // (k_tally wrote the pass's statistics into r->hostStats)
@@ -1151,7 +1182,7 @@ bool runPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t st
         r->reqShadows[l] = static_cast<int64_t>(hs[kStatReqShadows + l]);
     }
     r->overflowMask = static_cast<int>(hs[kStatOverflow]);
-    r->reqPaths = static_cast<int64_t>(std::min(r->chunkSlots, std::max(1, r->nSlots))) * spp;
+    r->reqPaths = std::min<int64_t>(r->chunkSlots, std::max<int64_t>(1, passSlots(r))) * spp;
     if (hs[kStatOverflow] != 0) return false;
     fs->rays += hs[kStatRays];
     fs->shadowRays += hs[kStatShadowRays];
@@ -1249,9 +1280,11 @@ void addStats(mrt_frame_stats& a, const mrt_frame_stats& b) {
 // by the pass: a copy is kept to redo a pass whose queues overflowed (with replanned queues).
 void renderProgressiveSample(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t st, int smp,
                              mrt_frame_stats* fs) {
-    const size_t npx = static_cast<size_t>(r->cfg.width) * static_cast<size_t>(r->cfg.height);
+    // (a batch of views: every view's bitmap, or the packed buffer's views x nSlots entries)
+    const size_t npx = static_cast<size_t>(r->cfg.width) * static_cast<size_t>(r->cfg.height) *
+                       static_cast<size_t>(std::max(1, r->views));
     int32_t* acc = dBitmap != nullptr ? dBitmap : dPacked;
-    const size_t accN = dBitmap != nullptr ? npx : static_cast<size_t>(r->nSlots);
+    const size_t accN = dBitmap != nullptr ? npx : static_cast<size_t>(passSlots(r));
     if (r->dBackup == nullptr || r->backupN < accN) {
         r->dBackup = r->frameMem.alloc<int32_t>(accN);
         r->backupN = accN;
@@ -1286,7 +1319,8 @@ void renderFrameSingle(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipS
     r->replansFrame = 0;
     if (r->stopFlag.load()) return;  // stopRender zeroes samplesPixel_ (Renderer.cpp:97)
     const int spp = std::max(1, r->cfg.samplesPixel);
-    const size_t npx = static_cast<size_t>(r->cfg.width) * static_cast<size_t>(r->cfg.height);
+    const size_t npx = static_cast<size_t>(r->cfg.width) * static_cast<size_t>(r->cfg.height) *
+                       static_cast<size_t>(std::max(1, r->views));  // (a batch: every view's bitmap)
     mrt_frame_stats fs{};
     if (r->cfg.progressive == 0) {
         // An overflowed pass is redone with queues planned from what it asked for (same results): at
@@ -1583,6 +1617,73 @@ int guarded(F&& f) {
     return -1;
 }
 
+// The camera of mrt_set_camera's arguments (`who`: the entry point, for the messages).
+mrt::GCamera cameraOf(const std::string& who, int32_t kind, const float* position, const float* lookAt, const float* up,
+                      float a, float b) {
+    if (!std::isfinite(a) || !std::isfinite(b)) throw std::runtime_error(who + ": non-finite field of view / size");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(position[k]) || !std::isfinite(lookAt[k]) || !std::isfinite(up[k]))
+            throw std::runtime_error(who + ": non-finite position / lookAt / up");
+    const mrt::v3 p{position[0], position[1], position[2]}, l{lookAt[0], lookAt[1], lookAt[2]}, u{up[0], up[1], up[2]};
+    if (kind == 0) return mrt::makePerspective(p, l, u, a, b);
+    if (kind == 1) return mrt::makeOrthographic(p, l, u, a, b);
+    throw std::runtime_error("camera kind: 0 perspective, 1 orthographic");
+}
+
+// ---- batches of views (mrt_render_views) -------------------------------------------------------
+// The argument checks, all before any device work; returns the views' cameras.
+std::vector<mrt::GCamera> checkViews(const mrt_renderer* r, const mrt_view* views, int32_t nViews, bool anyOutput) {
+    // (the views and the outputs first: those checks do not read the renderer)
+    if (r == nullptr || views == nullptr) throw std::runtime_error("mrt_render_views: null argument");
+    if (nViews <= 0) throw std::runtime_error("mrt_render_views: nViews must be >= 1");
+    std::vector<mrt::GCamera> cams;
+    for (int32_t v = 0; v < nViews; ++v) {
+        const mrt_view& w = views[v];
+        cams.push_back(cameraOf("mrt_render_views: view " + std::to_string(v), w.kind, w.position, w.lookAt, w.up, w.a, w.b));
+    }
+    if (!anyOutput) throw std::runtime_error("mrt_render_views: no output (bitmaps and packed buffer both null)");
+    if (!r->peers.empty())
+        throw std::runtime_error("mrt_render_views: device groups are not supported for batches of views");
+    // the virtual slot range and a chunk's paths are ints on the device
+    const int64_t total = static_cast<int64_t>(r->nSlots) * nViews;
+    const int64_t spp = std::max(1, r->cfg.samplesPixel);
+    const int64_t budget = r->cfg.maxPathsPerPass > 0 ? r->cfg.maxPathsPerPass : mrt::kPlanPathBudget;
+    const int64_t chunk = std::max<int64_t>(1, std::min(total, budget / spp));
+    if (total > 0x7fffffffLL || chunk * spp > 0x7fffffffLL)
+        throw std::runtime_error("mrt_render_views: nViews x pixelSlots (or a chunk's paths) beyond 2^31 - 1");
+    return cams;
+}
+
+// The batch as one frame over views x nSlots virtual slots (renderPass): the cameras uploaded on the
+// render stream, the renderer's own camera and slot count back in place afterwards (also on failure).
+void renderViews(mrt_renderer* r, const std::vector<mrt::GCamera>& cams, int32_t* dBitmaps, int32_t* dPacked,
+                 hipStream_t st, int32_t* hostBitmaps = nullptr) {
+    struct Restore {
+        mrt_renderer* r;
+        mrt::GCamera cam;
+        ~Restore() {
+            r->cam = cam;
+            r->views = 1;
+            r->batchCams = nullptr;
+        }
+    } restore{r, r->cam};
+    if (cams.size() == 1) {  // that single frame
+        r->cam = cams[0];
+        renderFrameSingle(r, dBitmaps, dPacked, st, hostBitmaps);
+        return;
+    }
+    if (r->viewCamsN < cams.size()) {
+        r->dViewCams = r->frameMem.alloc<mrt::GCamera>(cams.size());
+        r->viewCamsN = cams.size();
+    }
+    r->hostViewCams = cams;
+    MRT_HIP(hipMemcpyAsync(r->dViewCams, r->hostViewCams.data(), cams.size() * sizeof(mrt::GCamera),
+                           hipMemcpyHostToDevice, st));
+    r->views = static_cast<int>(cams.size());
+    r->batchCams = r->dViewCams;
+    renderFrameSingle(r, dBitmaps, dPacked, st, hostBitmaps);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1710,6 +1811,39 @@ int mrt_render_frame_device(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked,
     });
 }
 
+int mrt_render_views(mrt_renderer* r, const mrt_view* views, int32_t nViews, int32_t* bitmaps) {
+    return guarded([&] {
+        const std::vector<mrt::GCamera> cams = checkViews(r, views, nViews, bitmaps != nullptr);
+        MRT_HIP(hipSetDevice(r->device));
+        // the staging area: the frame's for one view, else views x width x height, grown on demand
+        const size_t n = static_cast<size_t>(r->cfg.width) * static_cast<size_t>(r->cfg.height) * cams.size();
+        int32_t* staging = r->dBitmap;
+        if (cams.size() > 1) {
+            if (r->viewBitmapsN < n) {
+                r->dViewBitmaps = r->frameMem.alloc<int32_t>(n);
+                r->viewBitmapsN = n;
+            }
+            staging = r->dViewBitmaps;
+        }
+        MRT_HIP(hipMemcpyAsync(staging, bitmaps, n * sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
+        renderViews(r, cams, staging, nullptr, r->stream, bitmaps);
+    });
+}
+
+int mrt_render_views_device(mrt_renderer* r, const mrt_view* views, int32_t nViews, int32_t* dBitmaps, int32_t* dPacked,
+                            void* stream) {
+    return guarded([&] {
+        const std::vector<mrt::GCamera> cams = checkViews(r, views, nViews, dBitmaps != nullptr || dPacked != nullptr);
+        MRT_HIP(hipSetDevice(r->device));
+        hipStream_t st = stream != nullptr ? static_cast<hipStream_t>(stream) : r->stream;
+        if (st != r->stream) {  // on the renderer's stream, after the caller's work (mrt_render_frame_device)
+            MRT_HIP(hipEventRecord(r->joinIn, st));
+            MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
+        }
+        renderViews(r, cams, dBitmaps, dPacked, r->stream);
+    });
+}
+
 int mrt_unpack_gathered(mrt_renderer* r, const int32_t* dGathered, int32_t* dBitmap, void* stream) {
     return guarded([&] {
         hipStream_t st = stream != nullptr ? static_cast<hipStream_t>(stream) : r->stream;
@@ -1753,20 +1887,7 @@ int mrt_set_camera(mrt_renderer* r, int32_t kind, const float* position, const f
     return guarded([&] {
         if (r == nullptr || position == nullptr || lookAt == nullptr || up == nullptr)
             throw std::runtime_error("mrt_set_camera: null argument");
-        if (!std::isfinite(a) || !std::isfinite(b)) throw std::runtime_error("mrt_set_camera: non-finite field of view / size");
-        for (int k = 0; k < 3; ++k)
-            if (!std::isfinite(position[k]) || !std::isfinite(lookAt[k]) || !std::isfinite(up[k]))
-                throw std::runtime_error("mrt_set_camera: non-finite position / lookAt / up");
-        const mrt::v3 p{position[0], position[1], position[2]}, l{lookAt[0], lookAt[1], lookAt[2]},
-            u{up[0], up[1], up[2]};
-        mrt::GCamera cam;
-        if (kind == 0) {
-            cam = mrt::makePerspective(p, l, u, a, b);
-        } else if (kind == 1) {
-            cam = mrt::makeOrthographic(p, l, u, a, b);
-        } else {
-            throw std::runtime_error("camera kind: 0 perspective, 1 orthographic");
-        }
+        const mrt::GCamera cam = cameraOf("mrt_set_camera", kind, position, lookAt, up, a, b);
         for (int i = 0; i < groupSize(r); ++i) shardOf(r, i)->cam = cam;
     });
 }
@@ -2113,7 +2234,8 @@ int mrt_get_queue_info(const mrt_renderer* r, mrt_queue_info* out, size_t size) 
     }
     mrt_queue_info q{};
     q.chunkSlots = r->plan.chunkSlots;
-    q.passes = (std::max(1, r->nSlots) + q.chunkSlots - 1) / std::max<int64_t>(1, q.chunkSlots);
+    // (the slot count the plan was made for: the shard's, or the last batch's views x the shard's)
+    q.passes = (std::max<int64_t>(1, r->planSlots) + q.chunkSlots - 1) / std::max<int64_t>(1, q.chunkSlots);
     q.queueBytes = r->plan.bytes;
     q.budgetBytes = r->planBudget;
     q.replans = r->replans;

@@ -18,7 +18,7 @@ from collections import defaultdict
 # lean PathTracer shading kernel
 # (k_trace_packet<false, 3, kGen>: kGen, round 6, the walk generating its camera rays; k_shade<2, false,
 # kRegen>: kRegen, level 1's shading regenerating them - both instantiations are the k_shade of levels 1-5)
-PRODUCT = {"k_trace": (r"k_trace<false, 1, 3>",), "k_trace_packet_shade": (r"k_trace_packet_shade<2, 3>",),
+PRODUCT = {"k_trace": (r"k_trace<false, 1, 3>",), "k_trace_packet_shade": (r"k_trace_packet_shade<2, 3, ",),
            "k_trace_packet": (r"k_trace_packet<false, 3, ",),
            "k_shadow": (r"k_shadow<false, 1, 3>",), "k_shade": (r"k_shade<2, false, ",)}
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
