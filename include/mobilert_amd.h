@@ -388,6 +388,14 @@ int mrt_kat_slab(const float *boxes, const float *orig, const float *dir, int32_
 /* Triangle::intersect (Triangle.cpp:63-109) as the kernels evaluate it: tris n x (A, B, C) xyz;
  * hit[i] = 1 and t[i] on an accepted hit (eps <= t < RayLengthMax). */
 int mrt_kat_triangle(const float *tris, const float *orig, const float *dir, int32_t n, int32_t *hit, float *t);
+/* The accumulation kernels on caller-given radiance: rgb holds nSlots x spp triples (slot-major,
+ * the samples of a slot in order), folded with incrementalAvg (Utils.cpp:66-90) as samples
+ * sampleBase .. sampleBase + spp - 1 into bitmap (width x height, read first when sampleBase > 0);
+ * slot q is the pixel a frame of that size gives it (nSlots at most the frame's slots).
+ * mode 0: k_accumulate; mode 1: k_resolve_accumulate with every vertex terminal.  *launched = 0
+ * (bitmap untouched) where mode 1 is not launched: spp does not divide 64. */
+int mrt_kat_accumulate(const float *rgb, int32_t nSlots, int32_t spp, int32_t sampleBase, int32_t width,
+                       int32_t height, int32_t mode, int32_t *bitmap, int32_t *launched);
 /* Arbitrary rays through the renderer's trace kernels (current walk and cull settings):
  * any = 0: closest hit (Shader::rayTrace intersection part, Shader.cpp:86-111): kind / index
  *          (input order, -1 on miss) / t per ray;

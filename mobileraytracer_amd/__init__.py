@@ -406,6 +406,21 @@ def kat_triangle(tris, orig, dirs):
     return hit, t
 
 
+def kat_accumulate(rgb, spp, sample_base, bitmap, width, height, mode=0):
+    """The accumulation kernels (incrementalAvg, Utils.cpp:66-90) on given radiance: rgb (nSlots * spp, 3)
+    float32, slot-major; bitmap (width * height) int32, read when sample_base > 0 and updated in
+    place; slot q is sharding.slot_pixels(width, height, 0, 1)[q].  mode 0: k_accumulate, 1:
+    k_resolve_accumulate (every vertex terminal).  False (bitmap untouched) where mode 1 is not
+    launched (spp does not divide 64)."""
+    c = np.ascontiguousarray(rgb, np.float32).reshape(-1, 3)
+    assert len(c) % spp == 0
+    assert bitmap.dtype == np.int32 and bitmap.size == width * height and bitmap.flags["C_CONTIGUOUS"]
+    launched = ctypes.c_int32(0)
+    _native.check(_native.lib().mrt_kat_accumulate(_ptr(c), len(c) // spp, spp, sample_base, width, height, mode,
+                                                   _ptr(bitmap), ctypes.byref(launched)))
+    return bool(launched.value)
+
+
 _active: List[Renderer] = []
 
 

@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = (
     "mrt_android_time_renderer", "mrt_android_sample", "mrt_android_number_of_lights", "mrt_android_resize",
     "mrt_android_vertices", "mrt_android_colors", "mrt_android_camera", "mrt_android_reset",
     "mrt_get_queue_info", "mrt_plan_queues", "mrt_render_views", "mrt_render_views_device",
+    "mrt_kat_accumulate",
     "RayTrace", "stopRender",
 )
 
@@ -191,6 +192,7 @@ def load_library(path=LIB_PATH):
         "mrt_sample_tables": (ctypes.c_int, [vp, vp, vp]),
         "mrt_kat_slab": (ctypes.c_int, [vp, vp, vp, ctypes.c_int32, vp]),
         "mrt_kat_triangle": (ctypes.c_int, [vp, vp, vp, ctypes.c_int32, vp, vp]),
+        "mrt_kat_accumulate": (ctypes.c_int, [vp] + [ctypes.c_int32] * 6 + [vp, P(ctypes.c_int32)]),
         "mrt_trace_rays": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():

@@ -83,6 +83,24 @@ MRT_HD float fastArcTan(float value) {
     return a - b * c;
 }
 
+// The reference's float -> uint32 conversion (static_cast<uint32_t> on x86-64: cvttss2si with a
+// 64-bit destination, of which the low 32 bits are kept): the low word of trunc(f) where
+// |f| < 2^63, and 0 for everything else, NaN included (the instruction's 0x8000000000000000).
+// The GPU's v_cvt_u32_f32 saturates instead (negative and NaN to 0, large to 0xFFFFFFFF), and the
+// plain cast is undefined outside [0, 2^32), so only that range takes it.
+// fitsU32: +0 <= f < 2^32, as one compare of f's bit pattern with 2^32's (a set sign bit, -0
+// included, and NaN compare above it and take the general path, which gives -0 its 0).
+MRT_HD bool fitsU32(float f) { return __builtin_bit_cast(uint32_t, f) < 0x4F800000u; }
+MRT_HD uint32_t x86TruncU32(float f) {
+    if (fitsU32(f)) return static_cast<uint32_t>(f);
+    if (!(f > -9223372036854775808.0F && f < 9223372036854775808.0F)) return 0u;
+    // 2^32 <= |f| < 2^63, or -2^32 < f <= -0: |f| truncated is below 2^63 and exact in 64 bits
+    const float a = f < 0.0F ? -f : f;
+    const uint64_t m = a < 4294967296.0F ? static_cast<uint64_t>(static_cast<uint32_t>(a))
+                                         : static_cast<uint64_t>(a);
+    return static_cast<uint32_t>(f < 0.0F ? 0u - m : m);
+}
+
 // Utils.cpp:66-90 incrementalAvg: float -> uint32 truncation, then pure uint32 arithmetic.
 MRT_HD int32_t incrementalAvg(v3 sample, int32_t avg, int32_t numSample) {
     const uint32_t avgU = static_cast<uint32_t>(avg);
@@ -90,9 +108,22 @@ MRT_HD int32_t incrementalAvg(v3 sample, int32_t avg, int32_t numSample) {
     const uint32_t lastR = avgU & 0xFFu;
     const uint32_t lastG = (avgU >> 8u) & 0xFFu;
     const uint32_t lastB = (avgU >> 16u) & 0xFFu;
-    const uint32_t sR = static_cast<uint32_t>(sample.x * 255.0F);
-    const uint32_t sG = static_cast<uint32_t>(sample.y * 255.0F);
-    const uint32_t sB = static_cast<uint32_t>(sample.z * 255.0F);
+    const float fR = sample.x * 255.0F, fG = sample.y * 255.0F, fB = sample.z * 255.0F;
+    uint32_t sR, sG, sB;
+    // ordinary radiance (the largest of the three bit patterns below 2^32's): plain converts
+    // behind one branch
+    const uint32_t bR = __builtin_bit_cast(uint32_t, fR), bG = __builtin_bit_cast(uint32_t, fG),
+                   bB = __builtin_bit_cast(uint32_t, fB);
+    const uint32_t bRG = bR > bG ? bR : bG;
+    if ((bRG > bB ? bRG : bB) < 0x4F800000u) {
+        sR = static_cast<uint32_t>(fR);
+        sG = static_cast<uint32_t>(fG);
+        sB = static_cast<uint32_t>(fB);
+    } else {
+        sR = x86TruncU32(fR);
+        sG = x86TruncU32(fG);
+        sB = x86TruncU32(fB);
+    }
     uint32_t cR = ((n - 1u) * lastR + sR) / n;
     uint32_t cG = ((n - 1u) * lastG + sG) / n;
     uint32_t cB = ((n - 1u) * lastB + sB) / n;

@@ -441,8 +441,10 @@ struct mrt_renderer {
 
 namespace {
 
-void buildUnits(mrt_renderer* r) {
-    const int W = r->cfg.width, H = r->cfg.height;
+// The pixel units of a W x H frame, split over rankCount shards: units[k] and their first slots
+// prefix[k] for rank k (also the map mrt_kat_accumulate gives the accumulation kernels)
+void frameUnits(int W, int H, int rankCount, std::vector<std::vector<int4>>* units,
+                std::vector<std::vector<int>>* prefix) {
     const int tilesPerSide = static_cast<int>(std::sqrt(static_cast<double>(mrt::kNumberOfTiles)));
     const int bx = W / tilesPerSide, by = H / tilesPerSide;  // Renderer.cpp:33-34
     if (bx <= 0 || by <= 0) throw std::runtime_error("width and height must be >= 16 (Renderer.cpp:33-38)");
@@ -470,20 +472,33 @@ void buildUnits(mrt_renderer* r) {
             while (h > 0 && (y0 + h - 1) * W + startX + bx - 1 >= resolution) --h;  // stay inside the bitmap
             if (h > 0) {
                 all.push_back(make_int4(startX, y0, bx, h));
-                owner.push_back(static_cast<int>((t + static_cast<size_t>(b)) % static_cast<size_t>(r->rankCount)));
+                owner.push_back(static_cast<int>((t + static_cast<size_t>(b)) % static_cast<size_t>(rankCount)));
             }
         }
     }
-    r->unitsByRank.assign(static_cast<size_t>(r->rankCount), {});
-    r->prefixByRank.assign(static_cast<size_t>(r->rankCount), {});
-    for (size_t u = 0; u < all.size(); ++u) r->unitsByRank[static_cast<size_t>(owner[u])].push_back(all[u]);
-    r->maxSlots = 0;
-    for (int k = 0; k < r->rankCount; ++k) {
+    units->assign(static_cast<size_t>(rankCount), {});
+    prefix->assign(static_cast<size_t>(rankCount), {});
+    for (size_t u = 0; u < all.size(); ++u) (*units)[static_cast<size_t>(owner[u])].push_back(all[u]);
+    for (int k = 0; k < rankCount; ++k) {
         int acc = 0;
-        for (const int4& u : r->unitsByRank[static_cast<size_t>(k)]) {
-            r->prefixByRank[static_cast<size_t>(k)].push_back(acc);
+        for (const int4& u : (*units)[static_cast<size_t>(k)]) {
+            (*prefix)[static_cast<size_t>(k)].push_back(acc);
             acc += u.z * u.w;
         }
+    }
+}
+
+int unitSlots(const std::vector<int4>& units) {
+    int acc = 0;
+    for (const int4& u : units) acc += u.z * u.w;
+    return acc;
+}
+
+void buildUnits(mrt_renderer* r) {
+    frameUnits(r->cfg.width, r->cfg.height, r->rankCount, &r->unitsByRank, &r->prefixByRank);
+    r->maxSlots = 0;
+    for (int k = 0; k < r->rankCount; ++k) {
+        const int acc = unitSlots(r->unitsByRank[static_cast<size_t>(k)]);
         if (k == r->rankIndex) r->nSlots = acc;
         r->maxSlots = std::max(r->maxSlots, acc);
     }
@@ -980,14 +995,16 @@ void renderPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t
     // returns at the depth cap (PathTracer.cpp:24-26, Whitted.cpp:15-17), so its closest-hit
     // walk is dead work and is skipped.  Not for textured scenes (rayTrace writes the texel Kd
     // before shade() returns, Shader.cpp:114-122).
-    const bool skipLast = r->skipLast != 0 && r->ds.textured == 0 &&
+    // Nor with a non-finite material (matsFinite): the level's zero records must then reach the
+    // parents' resolve (below), so the whole level runs as any other.
+    const bool skipLast = r->skipLast != 0 && r->ds.textured == 0 && r->ds.matsFinite != 0 &&
                           (shader == kShaderWhitted || shader == kShaderPathTracer) && nLevels > r->maxDepth;
     r->walkSkipped = skipLast;
     // ... and with it the level's shading (every record terminal, radiance 0) and resolve: the
     // parents' resolve treats the capped children as absent, which gives the same bits while
-    // every material is finite (Ks * 0 and Kd * 0 added to sums that start at +0), and the
-    // parents write no payload for them (only their count)
-    const bool skipLastShade = skipLast && nLevels >= 2 && r->ds.matsFinite != 0;
+    // every material is finite (Ks * 0 and Kd * 0 added to sums that start at +0; inf * 0 is
+    // NaN), and the parents write no payload for them (only their count)
+    const bool skipLastShade = skipLast && nLevels >= 2;
     // A batch of views is one longer slot range: virtual slot vs is slot vs % nSlots of view
     // vs / nSlots, so a chunk may begin and end inside a view and span several.  Only level 1 (ray
     // generation, the accumulation) maps a slot to its view; pathsPerLane and what follows from it
@@ -2397,6 +2414,62 @@ int mrt_kat_triangle(const float* tris, const float* orig, const float* dir, int
         mrt::launchKatTriangle(b.as<float>(), o.as<float>(), d.as<float>(), n, h.as<int32_t>(), tt.as<float>(), nullptr);
         MRT_HIP(hipMemcpy(hit, h.p, N * 4, hipMemcpyDeviceToHost));
         MRT_HIP(hipMemcpy(t, tt.p, N * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mrt_kat_accumulate(const float* rgb, int32_t nSlots, int32_t spp, int32_t sampleBase, int32_t width,
+                       int32_t height, int32_t mode, int32_t* bitmap, int32_t* launched) {
+    return guarded([&] {
+        using namespace mrt;
+        if (launched != nullptr) *launched = 0;
+        if (rgb == nullptr || bitmap == nullptr || launched == nullptr || spp <= 0 || sampleBase < 0 ||
+            (mode != 0 && mode != 1))
+            throw std::runtime_error("mrt_kat_accumulate: bad arguments");
+        std::vector<std::vector<int4>> units;
+        std::vector<std::vector<int>> prefix;
+        frameUnits(width, height, 1, &units, &prefix);
+        if (nSlots <= 0 || nSlots > unitSlots(units[0]) ||
+            static_cast<int64_t>(nSlots) * spp > (int64_t{1} << 24))
+            throw std::runtime_error("mrt_kat_accumulate: nSlots outside the frame's slots (or too many samples)");
+        const size_t n = static_cast<size_t>(nSlots) * static_cast<size_t>(spp);
+        const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
+        std::vector<float4> res(n);
+        for (size_t i = 0; i < n; ++i) res[i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0F);
+        const std::vector<int4> vtx(n, make_int4(-1, 0, 0, 0));  // every vertex terminal: its record is its radiance
+        DevBuf dRect(units[0].size() * sizeof(int4)), dPrefix(prefix[0].size() * sizeof(int)), dRes(n * sizeof(float4)),
+            dVtx(n * sizeof(int4)), dBitmap(pixels * sizeof(int32_t));
+        MRT_HIP(hipMemcpy(dRect.p, units[0].data(), units[0].size() * sizeof(int4), hipMemcpyHostToDevice));
+        MRT_HIP(hipMemcpy(dPrefix.p, prefix[0].data(), prefix[0].size() * sizeof(int), hipMemcpyHostToDevice));
+        MRT_HIP(hipMemcpy(dRes.p, res.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+        MRT_HIP(hipMemcpy(dVtx.p, vtx.data(), n * sizeof(int4), hipMemcpyHostToDevice));
+        MRT_HIP(hipMemcpy(dBitmap.p, bitmap, pixels * sizeof(int32_t), hipMemcpyHostToDevice));
+        AccumArgs aa{};
+        aa.map.rect = dRect.as<int4>();
+        aa.map.prefix = dPrefix.as<int>();
+        aa.map.nUnits = static_cast<int>(units[0].size());
+        aa.width = width;
+        aa.slotBase = 0;
+        aa.nSlots = nSlots;
+        aa.spp = spp;
+        aa.sampleBase = sampleBase;
+        if (mode == 0) {
+            launchAccumulate(aa, dRes.as<float4>(), dBitmap.as<int32_t>(), nullptr, nullptr);
+            *launched = 1;
+        } else {
+            DScene ds{};  // untextured; a terminal vertex reads nothing else of the scene
+            Level lv{}, nx{};
+            lv.res = dRes.as<float4>();
+            lv.vtx = dVtx.as<int4>();
+            lv.cap = static_cast<int>(n);
+            const ShadeArgs sa{1, 1, {0.0F, 0.0F, 0.0F}, nullptr};
+            *launched = launchResolveAccumulate(kShaderPathTracer, ds, lv, nx, sa, false, aa, dBitmap.as<int32_t>(),
+                                                nullptr, nullptr)
+                            ? 1
+                            : 0;
+        }
+        MRT_HIP(hipGetLastError());
+        MRT_HIP(hipDeviceSynchronize());
+        if (*launched != 0) MRT_HIP(hipMemcpy(bitmap, dBitmap.p, pixels * sizeof(int32_t), hipMemcpyDeviceToHost));
     });
 }
 
