@@ -13,6 +13,8 @@
  *   mrt_render_frame_device   the same, bitmap resident in device memory (no PCIe in the window)
  *   mrt_render_views[_device] a loop of Renderer::renderFrame over several cameras of one scene,
  *                             as one submission (no single reference call)
+ *   mrt_cast_rays_device      Shader::rayTrace's intersection part / Shader::shadowTrace for a batch of
+ *                             the caller's rays, resident in device memory (no single reference call)
  *   mrt_stop_render           Renderer::stopRender (Renderer.cpp:93-99); JNI rtStopRender
  *   mrt_get_sample            Renderer::getSample (Renderer.cpp:177-179); JNI rtGetSample
  *   mrt_get_total_casted_rays Renderer::getTotalCastedRays (Renderer.cpp:204-207)
@@ -403,6 +405,55 @@ int mrt_kat_accumulate(const float *rgb, int32_t nSlots, int32_t spp, int32_t sa
  * src: NULL or n pairs (kind, input index) of the primitive each ray leaves (self-exclusion). */
 int mrt_trace_rays(mrt_renderer *r, const float *orig, const float *dir, const float *dist, const int32_t *src,
                    int32_t n, int32_t any, int32_t *kind, int32_t *index, float *t);
+
+/* ---- ray queries (on the GPU; beyond the reference's entry points) ----
+ * mrt_cast_rays_device: a caller-supplied batch of rays through the renderer's walks, rays and results
+ * resident in device memory.  The results are those of Shader::rayTrace's intersection part
+ * (Shader.cpp:86-111) and of Shader::shadowTrace (Shader.cpp:132-158), bit for bit: what
+ * mrt_trace_rays returns for the same rays under the same walk and cull settings.
+ *
+ * Stream order, no host synchronisation: the work runs on the renderer's stream after everything
+ * enqueued on `stream` before the call, and `stream`'s later work waits for it; the call returns
+ * after enqueuing (no stream synchronisation, no device-to-host copy, and after a renderer's first
+ * query no allocation).  stream NULL: the renderer's own stream, with no ordering against any other.
+ * The batch structure is read during the call; the device arrays it names must stay valid until the
+ * work has run.
+ * Any n: a batch larger than the level-1 wavefront queue (mrt_queue_info.rayCap[0]; any hit:
+ * shadowCap[0]) is walked in chunks of that size, enqueued back to back, the queue counters reset on
+ * the device in between.  The queue plan in use at the call is the one read: a replan, or a switch
+ * between frames and batches of views, between two calls is harmless.
+ * Sources: a ray that leaves a triangle or a plane excludes it from its own test, as the reference's
+ * rays do (Triangle.cpp:64, Plane.cpp:39).  A sphere or light pair is accepted and changes nothing:
+ * the reference's spheres do not exclude themselves, and its shaders never continue a ray from a
+ * light, so the walks test lights without self-exclusion (as for mrt_trace_rays).
+ * src pairs (kind 1 plane / 2 sphere / 3 triangle / 4 light, index in the scene's input order) are
+ * mapped to the walk's order on the device; a pair whose kind is not 1-4 or whose index is outside
+ * that kind's range carries no source, as src == NULL does for every ray, and nothing is read out of
+ * bounds for it.  The mapping tables are made at a renderer's first query, kept until mrt_destroy
+ * and counted in mrt_scene_info.deviceBytes from then on.
+ * State: a query uses the level-1 queue arrays and the queue counters, nothing else.  Frames and
+ * batches of views rendered afterwards have the bits and ray counts they would have had without it;
+ * mrt_get_total_casted_rays and mrt_get_frame_stats do not see queries.
+ * A device group (deviceCount > 1) is refused: -1, nothing done.  Argument errors (a NULL handle or
+ * batch, NULL orig or dir, NULL dist with any, n outside 1 .. 2^31 - 1, a stride of 1, 2 or below 0,
+ * every wanted output NULL) return -1 before any device work, with a message in mrt_last_error();
+ * the batch and the outputs are checked before the renderer is read. */
+typedef struct mrt_ray_batch {
+    const float   *orig;        /* device: ray i's origin xyz at orig + i * origStride */
+    const float   *dir;         /* device: ray i's direction xyz at dir + i * dirStride */
+    const float   *dist;        /* device, any-hit only: tmax per ray (n floats); ignored for closest hit */
+    const int32_t *src;         /* device or NULL: n pairs (kind, input index) of the primitive a ray leaves */
+    int64_t origStride;         /* in floats, >= 3; 0 means 3.  6 reads an (n, 6) origin|direction array */
+    int64_t dirStride;
+    int64_t n;                  /* 1 .. 2^31 - 1 */
+} mrt_ray_batch;
+
+/* any = 0: d_kind / d_index / d_t per ray as mrt_trace_rays (kind 0 miss .. 4 light, index in the
+ *          scene's input order, -1 on a miss, t as the walk leaves it);
+ * any = 1: d_kind[i] = 1 occluded within dist[i], else 0; d_index / d_t are not written.
+ * Each output may be NULL (not wanted); at least one wanted output must be non-NULL. */
+int mrt_cast_rays_device(mrt_renderer *r, const mrt_ray_batch *rays, int32_t any,
+                         int32_t *d_kind, int32_t *d_index, float *d_t, void *stream);
 
 #ifdef __cplusplus
 }

@@ -247,6 +247,88 @@ class Renderer:
                                                n, int(any_hit), _ptr(k), _ptr(i), _ptr(t)))
         return k, i, t
 
+    # -- ray queries ---------------------------------------------------------------------
+    def cast_rays_device(self, d_orig: int, d_dir: int, n: int, *, d_dist: int = 0, d_src: int = 0,
+                         orig_stride: int = 3, dir_stride: int = 3, any_hit: bool = False, d_kind: int = 0,
+                         d_index: int = 0, d_t: int = 0, stream: int = 0) -> None:
+        """mrt_cast_rays_device: ``n`` rays resident in device memory through the walks, the results
+        into device memory (pointers as ints, e.g. torch ``data_ptr()``; strides in floats).  Closest
+        hit: ``d_kind`` / ``d_index`` int32 and ``d_t`` float32 per ray, as trace_rays; ``any_hit``:
+        ``d_kind`` = occluded within ``d_dist[i]``, nothing else written.  ``d_src``: (n, 2) int32
+        (kind, input index) of the primitive each ray leaves, or 0.  Outputs passed as 0 are not
+        written.  The work is ordered after ``stream``'s earlier work and before its later work, and
+        the call returns after enqueuing it; ``stream`` 0 is the renderer's own stream."""
+        batch = _native.MrtRayBatch(d_orig or None, d_dir or None, d_dist or None, d_src or None,
+                                    int(orig_stride), int(dir_stride), int(n))
+        _native.check(self._lib.mrt_cast_rays_device(
+            self._h, ctypes.byref(batch), int(bool(any_hit)), ctypes.c_void_p(d_kind or None),
+            ctypes.c_void_p(d_index or None), ctypes.c_void_p(d_t or None), ctypes.c_void_p(stream or None)))
+
+    def cast_rays(self, orig, dirs, dist=None, src=None, any_hit=False):
+        """cast_rays_device for torch tensors on the renderer's device: ``orig`` / ``dirs`` float32 of
+        shape (n, >= 3); ``dist`` float32 (n,), ``src`` int32 (n, 2).  Rows that are at least 3
+        floats apart with adjacent columns are read in place (a slice of a wider array: the strides
+        are taken from the tensors); any other layout - a broadcast ``expand`` of one origin, whose
+        rows are 0 apart, transposed columns - is made contiguous first.  Returns (kind, index, t),
+        or with ``any_hit`` the occlusion flags (int32), allocated and ordered on torch's current
+        stream; nothing is copied to the host and nothing waits for the device.  An empty batch
+        returns empty tensors (the C entry point itself takes 1 .. 2^31 - 1 rays).  Raises
+        ValueError for a tensor that is not on the renderer's GPU or has another shape."""
+        import torch
+
+        device = orig.device
+        want = self.config.device if not self.config.devices else -1
+        if not orig.is_cuda or (want >= 0 and device.index != want):
+            raise ValueError("orig: a tensor on the renderer's GPU (it is on %s)" % device)
+        n = orig.shape[0] if orig.dim() == 2 else -1
+
+        def rows(a, name):
+            """The tensor to read and its row stride in floats; never 0, which the C entry point
+            takes for 'packed' (rows 3 apart)."""
+            if a.device != device or a.dtype != torch.float32 or a.dim() != 2 or a.shape[0] != n or a.shape[1] < 3:
+                raise ValueError("%s: a float32 tensor of shape (%d, >= 3) on %s" % (name, n, device))
+            if a.stride(1) != 1 or (n > 1 and a.stride(0) < 3):
+                a = a[:, :3].contiguous()
+            return a, (a.stride(0) if n > 1 else 3)
+
+        orig, orig_stride = rows(orig, "orig")
+        dirs, dir_stride = rows(dirs, "dirs")
+        if any_hit:
+            if dist is None:
+                raise ValueError("any_hit needs dist")
+            if dist.device != device or dist.shape != (n,):
+                raise ValueError("dist: a tensor of shape (%d,) on %s" % (n, device))
+            dist = dist.to(torch.float32).contiguous()
+        if src is not None:
+            if src.device != device or src.shape != (n, 2):
+                raise ValueError("src: a tensor of shape (%d, 2) on %s" % (n, device))
+            src = src.to(torch.int32).contiguous()
+        kind = torch.empty(n, dtype=torch.int32, device=device)
+        index = None if any_hit else torch.empty(n, dtype=torch.int32, device=device)
+        t = None if any_hit else torch.empty(n, dtype=torch.float32, device=device)
+        if n == 0:
+            return kind if any_hit else (kind, index, t)
+        # Handle 0 would mean the renderer's own stream, which is not ordered against torch's null
+        # stream: from there the query goes through a stream of this renderer's, joined to the null
+        # stream by torch on both sides (events only; nothing waits on the host).
+        current = torch.cuda.current_stream(device)
+        via = current
+        if current.cuda_stream == 0:
+            via = getattr(self, "_query_stream", None)
+            if via is None:
+                via = self._query_stream = torch.cuda.Stream(device)
+            via.wait_stream(current)
+        try:
+            self.cast_rays_device(orig.data_ptr(), dirs.data_ptr(), n, d_dist=dist.data_ptr() if any_hit else 0,
+                                  d_src=src.data_ptr() if src is not None else 0, orig_stride=orig_stride,
+                                  dir_stride=dir_stride, any_hit=any_hit, d_kind=kind.data_ptr(),
+                                  d_index=0 if any_hit else index.data_ptr(), d_t=0 if any_hit else t.data_ptr(),
+                                  stream=via.cuda_stream)
+        finally:
+            if via is not current:
+                current.wait_stream(via)
+        return kind if any_hit else (kind, index, t)
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.mrt_destroy(self._h)

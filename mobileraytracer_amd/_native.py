@@ -26,7 +26,7 @@ EXPORTED_SYMBOLS = (
     "mrt_android_time_renderer", "mrt_android_sample", "mrt_android_number_of_lights", "mrt_android_resize",
     "mrt_android_vertices", "mrt_android_colors", "mrt_android_camera", "mrt_android_reset",
     "mrt_get_queue_info", "mrt_plan_queues", "mrt_render_views", "mrt_render_views_device",
-    "mrt_kat_accumulate",
+    "mrt_kat_accumulate", "mrt_cast_rays_device",
     "RayTrace", "stopRender",
 )
 
@@ -57,6 +57,11 @@ class MrtBlob(ctypes.Structure):
 class MrtView(ctypes.Structure):  # mrt_view: the arguments of mrt_set_camera
     _fields_ = [("kind", ctypes.c_int32), ("position", ctypes.c_float * 3), ("lookAt", ctypes.c_float * 3),
                 ("up", ctypes.c_float * 3), ("a", ctypes.c_float), ("b", ctypes.c_float)]
+
+
+class MrtRayBatch(ctypes.Structure):  # mrt_ray_batch: a device-resident batch of rays (mrt_cast_rays_device)
+    _fields_ = [("orig", ctypes.c_void_p), ("dir", ctypes.c_void_p), ("dist", ctypes.c_void_p), ("src", ctypes.c_void_p),
+                ("origStride", ctypes.c_int64), ("dirStride", ctypes.c_int64), ("n", ctypes.c_int64)]
 
 
 class MrtSceneInfo(ctypes.Structure):
@@ -194,6 +199,7 @@ def load_library(path=LIB_PATH):
         "mrt_kat_triangle": (ctypes.c_int, [vp, vp, vp, ctypes.c_int32, vp, vp]),
         "mrt_kat_accumulate": (ctypes.c_int, [vp] + [ctypes.c_int32] * 6 + [vp, P(ctypes.c_int32)]),
         "mrt_trace_rays": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]),
+        "mrt_cast_rays_device": (ctypes.c_int, [vp, P(MrtRayBatch), ctypes.c_int32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("MOBILERT_LIB") and not hasattr(lib, name):

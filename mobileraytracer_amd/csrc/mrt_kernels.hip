@@ -1265,6 +1265,85 @@ void launchLoadRays(const Level& lv, const float* orig, const float* dir, const 
 }
 
 // ---------------------------------------------------------------------------------------
+// Ray queries (mrt_cast_rays_device): the caller's device-resident rays into level 1's queue, and the
+// walk's results back out, one thread per ray.  Both are bandwidth kernels: adjacent lanes read
+// adjacent 12-byte (or stride-sized) ray records, so the three dword loads of a wave cover one
+// contiguous range, and the queue records are written as whole 16-byte stores.
+
+// (kind, input index) of the primitive a ray leaves -> the walk's BVH-order code; anything that
+// names no primitive of the scene (a kind outside 1-4, an index outside the kind's range) is no
+// source, and no table is read for it.
+__device__ __forceinline__ uint32_t querySource(const QueryTables& tb, int32_t k, int32_t j) {
+    const int32_t* inv = k == static_cast<int32_t>(kTriangle) ? tb.triInv
+                         : k == static_cast<int32_t>(kPlane)  ? tb.planeInv
+                         : k == static_cast<int32_t>(kSphere) ? tb.sphereInv
+                                                              : nullptr;
+    const int32_t count = k == static_cast<int32_t>(kTriangle) ? tb.nTri
+                          : k == static_cast<int32_t>(kPlane)  ? tb.nPlanes
+                          : k == static_cast<int32_t>(kSphere) ? tb.nSpheres
+                          : k == static_cast<int32_t>(kLight)  ? tb.nLights
+                                                               : 0;
+    if (static_cast<uint32_t>(j) >= static_cast<uint32_t>(count)) return kNoPrim;  // (negative j: a huge unsigned)
+    const int32_t b = inv != nullptr ? inv[j] : j;  // (lights keep their input order)
+    return encodePrim(static_cast<uint32_t>(k), static_cast<uint32_t>(b));
+}
+
+__global__ __launch_bounds__(256) void k_query_load(Level lv, QueryRays q, QueryTables tb, int n, int any, int* counters) {
+    const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i == 0) denseCounts(counters, 1, any != 0, n, any ? lv.shadowSegCap : lv.segCap);
+    if (i >= n) return;
+    const long long g = q.base + i;  // the ray's index in the caller's batch
+    const float* o = q.orig + g * q.origStride;
+    const float* d = q.dir + g * q.dirStride;
+    const float ox = o[0], oy = o[1], oz = o[2];
+    const float dx = d[0], dy = d[1], dz = d[2];
+    uint32_t code = kNoPrim;
+    if (q.src != nullptr) code = querySource(tb, q.src[2 * g], q.src[2 * g + 1]);
+    if (any) {
+        lv.sO[i] = make_float4(ox, oy, oz, bitsf(code));
+        lv.sD[i] = make_float4(dx, dy, dz, q.dist[g]);
+        lv.sC[i] = make_float4(0.0F, 0.0F, 0.0F, -1.0F);
+    } else {
+        lv.rO[i] = make_float4(ox, oy, oz, 0.0F);
+        lv.rD[i] = make_float4(dx, dy, dz, bitsf(code));
+        lv.tree[i] = 1u;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_query_store(Level lv, QueryTables tb, int n, int any, long long base,
+                                                     int32_t* kind, int32_t* index, float* t) {
+    const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const long long g = base + i;
+    if (any) {
+        if (kind != nullptr) kind[g] = lv.sC[i].w != 0.0F ? 1 : 0;
+        return;
+    }
+    const float4 h = lv.hit[i];
+    const uint32_t code = fbits(h.w);
+    const uint32_t k = primKind(code);
+    if (kind != nullptr) kind[g] = static_cast<int32_t>(k);
+    if (index != nullptr) {
+        const int32_t* order = k == kTriangle ? tb.triOrder : k == kPlane ? tb.planeOrder : k == kSphere ? tb.sphereOrder : nullptr;
+        const int32_t b = static_cast<int32_t>(primIndex(code));
+        index[g] = k == kMiss ? -1 : order != nullptr ? order[b] : b;
+    }
+    if (t != nullptr) t[g] = h.x;
+}
+
+void launchQueryLoad(const Level& lv, const QueryRays& q, const QueryTables& tb, int n, bool any, int* counters,
+                     hipStream_t st) {
+    hipLaunchKernelGGL(k_query_load, dim3(std::max(1, (n + 255) / 256)), dim3(256), 0, st, lv, q, tb, n, any ? 1 : 0,
+                       counters);
+}
+
+void launchQueryStore(const Level& lv, const QueryTables& tb, int n, bool any, long long base, int32_t* kind,
+                      int32_t* index, float* t, hipStream_t st) {
+    hipLaunchKernelGGL(k_query_store, dim3(std::max(1, (n + 255) / 256)), dim3(256), 0, st, lv, tb, n, any ? 1 : 0, base,
+                       kind, index, t);
+}
+
+// ---------------------------------------------------------------------------------------
 // launch wrappers
 void launchRaygen(const RaygenArgs& a, const Level& lv, int* counters, hipStream_t st) {
     const int blocks = (a.nPaths + 255) / 256;

@@ -259,6 +259,37 @@ void launchKatTriangle(const float* tris, const float* orig, const float* dir, i
                        hipStream_t st);
 void launchLoadRays(const Level& lv, const float* orig, const float* dir, const float* dist, const uint32_t* src, int n,
                     bool any, int* counters, hipStream_t st);
+// Ray queries (mrt_cast_rays_device).  A chunk of the caller's device-resident batch: ray base + i
+// (i < n, the launch's count) is read at orig + (base + i) * origStride, its source pair at
+// src + 2 (base + i); 64-bit, the batch may hold 2^31 - 1 rays of any stride.
+struct QueryRays {
+    const float* orig;
+    const float* dir;
+    const float* dist;   // any hit: tmax per ray; else not read
+    const int32_t* src;  // (kind, input index) pairs, or null
+    long long origStride, dirStride;  // in floats
+    long long base;
+};
+// The scene's primitive orders on the device: *Inv[input index] = BVH-order index (a source pair ->
+// the walk's primitive code), *Order[BVH-order index] = input index (a hit -> the caller's index),
+// and each kind's count (a source pair outside it names nothing).  Lights keep their input order.
+struct QueryTables {
+    const int32_t* triInv;
+    const int32_t* planeInv;
+    const int32_t* sphereInv;
+    const int32_t* triOrder;
+    const int32_t* planeOrder;
+    const int32_t* sphereOrder;
+    int32_t nTri, nPlanes, nSpheres, nLights;
+};
+// k_query_load: n rays of q into lv's queue (rO / rD / tree, or with any sO / sD / sC) with the dense
+// segment counts, as launchLoadRays; n at most lv.cap (any: lv.shadowCap)
+void launchQueryLoad(const Level& lv, const QueryRays& q, const QueryTables& tb, int n, bool any, int* counters,
+                     hipStream_t st);
+// k_query_store: the walk's results of those n rays to kind / index / t at base + i (null: not
+// written); any: kind = occluded, nothing else
+void launchQueryStore(const Level& lv, const QueryTables& tb, int n, bool any, long long base, int32_t* kind,
+                      int32_t* index, float* t, hipStream_t st);
 int traceResidentThreadsPerCU();  // max over the trace walks of resident threads per CU
 // out[2 slot], out[2 slot + 1] = real-time counter (100 MHz) before / after a spin of `ticks`
 void launchSpin(unsigned long long* out, int slot, unsigned long long ticks, hipStream_t st);

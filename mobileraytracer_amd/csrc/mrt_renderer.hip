@@ -385,6 +385,11 @@ struct mrt_renderer {
     std::vector<mrt::GCamera> hostViewCams;  // the upload's source
     int32_t* dViewBitmaps = nullptr;         // the host entry point's staging: views x width x height
     size_t viewBitmapsN = 0;
+    // Ray queries (mrt_cast_rays_device): the primitive orders on the device, made at the first query
+    // (the forward tables uploaded into queryMem; the inverse ones are the scene's, DScene::triNaive ...)
+    DeviceMem queryMem;
+    mrt::QueryTables queryTables{};
+    bool queryReady = false;
     int64_t planSlots = 0;                   // the (virtual) slot count the queue plan was made for
     hipStream_t stream = nullptr;
     int overlap = 1;                     // tuning key 3: shadow rays on their own stream
@@ -1701,6 +1706,85 @@ void renderViews(mrt_renderer* r, const std::vector<mrt::GCamera>& cams, int32_t
     renderFrameSingle(r, dBitmaps, dPacked, st, hostBitmaps);
 }
 
+// ---- ray queries (mrt_cast_rays_device) --------------------------------------------------------
+// The argument checks, all before any device work; returns the batch with its strides resolved.
+mrt::QueryRays checkRayBatch(const mrt_renderer* r, const mrt_ray_batch* rays, int32_t any, const int32_t* dKind,
+                             const int32_t* dIndex, const float* dT) {
+    // (the batch and the outputs first: those checks do not read the renderer)
+    if (r == nullptr) throw std::runtime_error("mrt_cast_rays_device: null renderer");
+    if (rays == nullptr) throw std::runtime_error("mrt_cast_rays_device: null ray batch");
+    if (rays->orig == nullptr || rays->dir == nullptr) throw std::runtime_error("mrt_cast_rays_device: null orig / dir");
+    if (any != 0 && rays->dist == nullptr) throw std::runtime_error("mrt_cast_rays_device: any hit needs dist (null)");
+    if (rays->n < 1 || rays->n > 0x7fffffffLL) throw std::runtime_error("mrt_cast_rays_device: n must be 1 .. 2^31 - 1");
+    auto stride = [](int64_t s, const char* name) -> long long {
+        if (s == 0) return 3;
+        if (s < 3) throw std::runtime_error(std::string("mrt_cast_rays_device: ") + name + " must be 0 (packed) or >= 3 floats");
+        return s;
+    };
+    mrt::QueryRays q{};
+    q.orig = rays->orig;
+    q.dir = rays->dir;
+    q.dist = any != 0 ? rays->dist : nullptr;
+    q.src = rays->src;
+    q.origStride = stride(rays->origStride, "origStride");
+    q.dirStride = stride(rays->dirStride, "dirStride");
+    if (any != 0 ? dKind == nullptr : (dKind == nullptr && dIndex == nullptr && dT == nullptr))
+        throw std::runtime_error(any != 0 ? "mrt_cast_rays_device: no output (d_kind null; any hit writes nothing else)"
+                                          : "mrt_cast_rays_device: no output (d_kind, d_index and d_t all null)");
+    if (!r->peers.empty()) throw std::runtime_error("mrt_cast_rays_device: device groups are not supported for ray queries");
+    return q;
+}
+
+// The query's device tables, made once per renderer: the forward orders uploaded on the render stream
+// (before the first query's kernels), the inverse ones shared with the scene.
+const mrt::QueryTables& queryTables(mrt_renderer* r) {
+    if (!r->queryReady) {
+        mrt::QueryTables& tb = r->queryTables;
+        tb.triOrder = r->queryMem.upload(r->triOrder, r->stream);
+        tb.planeOrder = r->queryMem.upload(r->planeOrder, r->stream);
+        tb.sphereOrder = r->queryMem.upload(r->sphereOrder, r->stream);
+        tb.triInv = r->ds.triNaive;
+        tb.planeInv = r->ds.planeNaive;
+        tb.sphereInv = r->ds.sphereNaive;
+        tb.nTri = static_cast<int32_t>(r->triOrder.size());
+        tb.nPlanes = static_cast<int32_t>(r->planeOrder.size());
+        tb.nSpheres = static_cast<int32_t>(r->sphereOrder.size());
+        tb.nLights = r->ds.nLights;
+        r->queryReady = true;
+    }
+    return r->queryTables;
+}
+
+// The batch through level 1's queue, a chunk of its capacity at a time, all enqueued on the render
+// stream: counters reset, rays loaded, walked, results stored.  Nothing waits on the host.
+void castRays(mrt_renderer* r, mrt::QueryRays q, int64_t n, bool any, int32_t* dKind, int32_t* dIndex, float* dT) {
+    using namespace mrt;
+    hipStream_t st = r->stream;
+    const QueryTables& tb = queryTables(r);
+    mrt_renderer::Pipe& pp = r->pipe;
+    const Level& lv = pp.levels[1];  // (the plan in use now: a frame or a batch of views may have re-made it)
+    const int64_t cap = any ? std::min<int64_t>(lv.shadowCap, static_cast<int64_t>(kQueueSegs) * lv.shadowSegCap)
+                            : std::min<int64_t>(lv.cap, static_cast<int64_t>(kQueueSegs) * lv.segCap);
+    if (cap <= 0) throw std::runtime_error("mrt_cast_rays_device: the level-1 queue holds no rays");
+    // the walk launches' thread cap as a frame's (renderPass): tuning key 28 narrows the grid.  The
+    // diagnostic mrt_trace_rays launches the full grid whatever the key; every grid walks every ray,
+    // so the results are the same and only the launches differ.
+    const int walkThreads = r->walkGridCap > 0 ? std::min(r->traceThreads, r->walkGridCap * kBlock) : r->traceThreads;
+    for (int64_t base = 0; base < n; base += cap) {
+        const int m = static_cast<int>(std::min<int64_t>(cap, n - base));
+        q.base = base;
+        MRT_HIP(hipMemsetAsync(pp.counters, 0, sizeof(int) * kNumCounters, st));
+        r->countersClean = false;  // (left in use: the next pass resets them)
+        launchQueryLoad(lv, q, tb, m, any, pp.counters, st);
+        if (any)
+            launchShadow(r->ds, lv, pp.counters, 1, pp.gstackShadow, r->gdepth, pp.stats, false, walkThreads, st);
+        else
+            launchTrace(r->ds, lv, pp.counters, 1, pp.gstack, r->gdepth, pp.stats, false, walkThreads, st);
+        launchQueryStore(lv, tb, m, any, base, dKind, dIndex, dT, st);
+    }
+    MRT_HIP(hipGetLastError());
+}
+
 }  // namespace
 
 extern "C" {
@@ -1861,6 +1945,26 @@ int mrt_render_views_device(mrt_renderer* r, const mrt_view* views, int32_t nVie
     });
 }
 
+int mrt_cast_rays_device(mrt_renderer* r, const mrt_ray_batch* rays, int32_t any, int32_t* dKind, int32_t* dIndex,
+                         float* dT, void* stream) {
+    return guarded([&] {
+        const mrt::QueryRays q = checkRayBatch(r, rays, any, dKind, dIndex, dT);
+        MRT_HIP(hipSetDevice(r->device));
+        hipStream_t st = stream != nullptr ? static_cast<hipStream_t>(stream) : r->stream;
+        // on the renderer's stream, after the caller's work and before the caller's next; the query
+        // itself never synchronises, so (unlike a frame) the second event is always needed
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinIn, st));
+            MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
+        }
+        castRays(r, q, rays->n, any != 0, dKind, dIndex, dT);
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinOut, r->stream));
+            MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
+        }
+    });
+}
+
 int mrt_unpack_gathered(mrt_renderer* r, const int32_t* dGathered, int32_t* dBitmap, void* stream) {
     return guarded([&] {
         hipStream_t st = stream != nullptr ? static_cast<hipStream_t>(stream) : r->stream;
@@ -1887,7 +1991,7 @@ int mrt_get_scene_info(const mrt_renderer* r, mrt_scene_info* info) {
     info->triangleBvhDepth = r->triDepth;
     info->pixelSlots = r->nSlots;
     info->pixelSlotsMax = r->maxSlots;
-    info->deviceBytes = static_cast<int64_t>(r->sceneMem.total + r->queueMem.total + r->frameMem.total);
+    info->deviceBytes = static_cast<int64_t>(r->sceneMem.total + r->queueMem.total + r->frameMem.total + r->queryMem.total);
     info->shadowStreamConcurrent = r->shadowConcurrent;
     info->shadowStreamsTried = r->shadowTries;
     info->deviceCount = groupSize(r);
