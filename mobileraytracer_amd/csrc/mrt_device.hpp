@@ -73,7 +73,7 @@ struct DScene {
     const float4* triTex;      // 2 per triangle: (tA.xy, tB.xy), (tC.xy, -, -)
     const int4* texInfo;       // per texture: width, height, channels, first byte in texels
     const uint8_t* texels;
-    int32_t textured;
+    int32_t textured;          // how many materials have a texture (0: none; > 1: the Kd replay walks subtrees)
     // Config::accelerator (Shader.hpp:20-24): 1 Naive, 2 RegularGrid, 3 BVH, anything else
     // builds no accelerator (only lights are hit, Shader.cpp:86-111)
     int32_t accel;

@@ -960,14 +960,58 @@ __global__ __launch_bounds__(kBlock) void k_shade_simple(DScene s, Level lv, int
 }
 
 // ---------------------------------------------------------------------------------------
-// kTex: a textured scene (the Kd replay below); untextured scenes run the lean instantiation
+// Scenes with several textured materials (kTex == 2): the last write to material matF in the subtree
+// of vertex c of level `level`, in the reference's depth-first order (a vertex's own write, then
+// its diffuse, specular and transmission subtrees), or w = -1.  `last` keeps a subtree's last write
+// whatever its material, so where that is a write to another material the subtree is walked in
+// reverse order through the levels' vtx / kd / last records (alive until the frame's last resolve),
+// skipping every subtree without a write.  Pending: at most 3 entries per level (a vertex's own
+// write and two of its subtrees).  Every index is checked against its level's capacity: an
+// overflowed pass (redone) leaves stale records behind.
+constexpr int kTexWalkStack = 3 * kMaxLevels + 4;
+__device__ __noinline__ float4 searchLastWrite(const TexLevel* tl, int level, int c, float matF) {
+    int2 stack[kTexWalkStack];  // (level, vertex); level < 0: the vertex's own write
+    int sp = 0;
+    stack[sp++] = make_int2(level, c);
+    while (sp > 0) {
+        const int2 e = stack[--sp];
+        if (e.x < 0) {
+            const float4 k = tl[-e.x].kd[e.y];
+            if (k.w == matF) return k;
+            continue;
+        }
+        const float4 l = tl[e.x].last[e.y];
+        if (l.w < 0.0F) continue;
+        if (l.w == matF) return l;
+        const int4 va = tl[e.x].vtx[e.y];
+        if (va.x < 0 || e.x + 1 >= kMaxLevels || sp + 4 > kTexWalkStack) continue;  // terminal: last is its own write
+        stack[sp++] = make_int2(-e.x, e.y);
+        const int cap = tl[e.x + 1].cap;
+        int j = va.z;
+#pragma unroll
+        for (int bit = 1; bit <= 4; bit <<= 1) {  // pushed D, S, T: popped T, S, D
+            if ((va.w & bit) == 0) continue;
+            if (j >= 0 && j < cap) stack[sp++] = make_int2(e.x + 1, j);
+            ++j;
+        }
+    }
+    return make_float4(0.0F, 0.0F, 0.0F, -1.0F);
+}
+// lastC: last[c] of that vertex, already loaded
+__device__ __forceinline__ float4 lastWriteIn(const TexLevel* tl, int level, int c, float4 lastC, float matF) {
+    if (c < 0 || lastC.w < 0.0F || lastC.w == matF) return c < 0 ? make_float4(0.0F, 0.0F, 0.0F, -1.0F) : lastC;
+    return searchLastWrite(tl, level, c, matF);
+}
+
+// kTex: 0 an untextured scene (the lean instantiation), 1 a scene with one textured material (the Kd
+// replay from the children's last-write records alone), 2 several (tl: the table of levels)
 // Vertex i of level `level`: its radiance from its shadow rays' flags and its children's results,
 // in the reference's float-op order (Whitted.cpp:36-92, PathTracer.cpp:22-142).
 // Returns the radiance (w: the hit-a-light flag), or for a terminal vertex (va.x < 0) the record
 // k_shade wrote; kLast: write the textured scenes' last-texel record for the level above.
-template <int kShader, bool kTex, bool kLast>
+template <int kShader, int kTex, bool kLast>
 __device__ __forceinline__ float4 resolveValue(const DScene& s, const Level& lv, const Level& nx, int i, int level,
-                                               const ShadeArgs& a, int deadChildren, int4 va) {
+                                               const ShadeArgs& a, int deadChildren, int4 va, const TexLevel* tl = nullptr) {
     {
         if (va.x < 0) return lv.res[i];  // terminal: res written by k_shade
         // children (consecutive from va.z in the order diffuse, specular, transmission); an
@@ -989,10 +1033,11 @@ __device__ __forceinline__ float4 resolveValue(const DScene& s, const Level& lv,
         v3 Kd = xyz(m[1]);
         const v3 Ks = xyz(m[2]), Kt = xyz(m[3]);
         // textured scenes: Kd as shade() reads it - this hit's texel until a child's subtree
-        // writes the material again (exact while at most one material is textured: the subtree
-        // records keep only its last write)
+        // writes the material again.  The subtree records keep only a subtree's last write: with
+        // one textured material that is the write shade() sees; with several (kTex == 2) a
+        // subtree that ends with a write to another material is searched (lastWriteIn)
         float4 lD = make_float4(0.0F, 0.0F, 0.0F, -1.0F), lS = lD, lT = lD, own = lD;
-        if (kTex) {
+        if (kTex != 0) {
             own = lv.kd[i];
             if (own.w >= 0.0F) Kd = xyz(own);
             if (vb.x >= 0) lD = nx.last[vb.x];
@@ -1018,7 +1063,17 @@ __device__ __forceinline__ float4 resolveValue(const DScene& s, const Level& lv,
             if (hasPositive(Ks) && vb.y >= 0) rgb = rgb + Ks * xyz(nx.res[vb.y]);
             if (hasPositive(Kt) && vb.z >= 0) rgb = rgb + Kt * xyz(nx.res[vb.z]);
             // the ambient term reads Kd after the specular and transmission subtrees
-            const v3 KdAmb = lT.w == matF ? xyz(lT) : ((lT.w < 0.0F && lS.w == matF) ? xyz(lS) : Kd);
+            v3 KdAmb;
+            if constexpr (kTex == 2) {
+                float4 f = make_float4(0.0F, 0.0F, 0.0F, -1.0F);
+                if (__float_as_int(m[1].w) >= 0) {  // (an untextured material's Kd is never written)
+                    f = lastWriteIn(tl, level + 1, vb.z, lT, matF);
+                    if (f.w < 0.0F) f = lastWriteIn(tl, level + 1, vb.y, lS, matF);
+                }
+                KdAmb = f.w >= 0.0F ? xyz(f) : Kd;
+            } else {
+                KdAmb = lT.w == matF ? xyz(lT) : ((lT.w < 0.0F && lS.w == matF) ? xyz(lS) : Kd);
+            }
             rgb = rgb + KdAmb * 0.1F;
             out = make_float4(rgb.x, rgb.y, rgb.z, 0.0F);
         } else {  // PathTracer.cpp:127-142
@@ -1027,7 +1082,13 @@ __device__ __forceinline__ float4 resolveValue(const DScene& s, const Level& lv,
             if (vb.x >= 0) {
                 const float4 r = nx.res[vb.x];
                 hitLight = r.w != 0.0F;
-                const v3 KdD = lD.w == matF ? xyz(lD) : Kd;  // Kd after the diffuse subtree
+                v3 KdD = lD.w == matF ? xyz(lD) : Kd;  // Kd after the diffuse subtree
+                if constexpr (kTex == 2) {
+                    if (lD.w >= 0.0F && lD.w != matF && __float_as_int(m[1].w) >= 0) {
+                        const float4 f = searchLastWrite(tl, level + 1, vb.x, matF);
+                        if (f.w >= 0.0F) KdD = xyz(f);
+                    }
+                }
                 LiD = LiD + KdD * xyz(r);
                 if (level > kRayDepthMin) LiD = LiD / (0.5F * 0.5F);
                 if (hasPositive(Ld) && hitLight) LiD = v3{0.0F, 0.0F, 0.0F};
@@ -1041,26 +1102,36 @@ __device__ __forceinline__ float4 resolveValue(const DScene& s, const Level& lv,
             rgb = rgb + LiT;
             out = make_float4(rgb.x, rgb.y, rgb.z, hitLight ? 1.0F : 0.0F);
         }
-        if (kTex && kLast) lv.last[i] = lT.w >= 0.0F ? lT : (lS.w >= 0.0F ? lS : (lD.w >= 0.0F ? lD : own));
+        if (kTex != 0 && kLast) lv.last[i] = lT.w >= 0.0F ? lT : (lS.w >= 0.0F ? lS : (lD.w >= 0.0F ? lD : own));
         return out;
     }
 }
 
-template <int kShader, bool kTex>
+template <int kShader, int kTex>
 __device__ __forceinline__ void resolveVertex(const DScene& s, const Level& lv, const Level& nx, int i, int level,
-                                              const ShadeArgs& a, int deadChildren) {
+                                              const ShadeArgs& a, int deadChildren, const TexLevel* tl = nullptr) {
     const int4 va = lv.vtx[i];
     if (va.x < 0) return;  // terminal: res written by k_shade
-    lv.res[i] = resolveValue<kShader, kTex, true>(s, lv, nx, i, level, a, deadChildren, va);
+    lv.res[i] = resolveValue<kShader, kTex, true>(s, lv, nx, i, level, a, deadChildren, va, tl);
 }
 
-template <int kShader, bool kTex>
+template <int kShader, int kTex>
 __global__ __launch_bounds__(256) void k_resolve(DScene s, Level lv, Level nx, int* counters, int level, ShadeArgs a,
                                                  int deadChildren) {
     const SegMap map = segMap(counters, level, false, lv.segCap);
     for (int vi = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x); vi < map.total();
          vi += static_cast<int>(gridDim.x * blockDim.x))
         resolveVertex<kShader, kTex>(s, lv, nx, map.phys(vi), level, a, deadChildren);
+}
+
+// ... of a scene with several textured materials (tl: the table of levels, lastWriteIn)
+template <int kShader>
+__global__ __launch_bounds__(256) void k_resolve_textures(DScene s, Level lv, Level nx, int* counters, int level,
+                                                          ShadeArgs a, int deadChildren, const TexLevel* tl) {
+    const SegMap map = segMap(counters, level, false, lv.segCap);
+    for (int vi = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x); vi < map.total();
+         vi += static_cast<int>(gridDim.x * blockDim.x))
+        resolveVertex<kShader, 2>(s, lv, nx, map.phys(vi), level, a, deadChildren, tl);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1535,19 +1606,24 @@ void launchShade(int shader, const DScene& s, const Level& lv, const Level& nx, 
 }
 
 void launchResolve(int shader, const DScene& s, const Level& lv, const Level& nx, int* counters, int level,
-                   const ShadeArgs& a, int grid, hipStream_t st, bool deadChildren) {
+                   const ShadeArgs& a, int grid, hipStream_t st, bool deadChildren, const TexLevel* texLevels) {
     const int dead = deadChildren ? 1 : 0;
     const bool tex = s.textured != 0;
+    const bool multi = s.textured > 1 && texLevels != nullptr;  // several textured materials
     if (shader == kShaderPathTracer) {
-        if (tex)
-            hipLaunchKernelGGL((k_resolve<kShaderPathTracer, true>), dim3(grid), dim3(256), 0, st, s, lv, nx, counters, level, a, dead);
+        if (multi)
+            hipLaunchKernelGGL(k_resolve_textures<kShaderPathTracer>, dim3(grid), dim3(256), 0, st, s, lv, nx, counters, level, a, dead, texLevels);
+        else if (tex)
+            hipLaunchKernelGGL((k_resolve<kShaderPathTracer, 1>), dim3(grid), dim3(256), 0, st, s, lv, nx, counters, level, a, dead);
         else
-            hipLaunchKernelGGL((k_resolve<kShaderPathTracer, false>), dim3(grid), dim3(256), 0, st, s, lv, nx, counters, level, a, dead);
+            hipLaunchKernelGGL((k_resolve<kShaderPathTracer, 0>), dim3(grid), dim3(256), 0, st, s, lv, nx, counters, level, a, dead);
     } else if (shader == kShaderWhitted) {
-        if (tex)
-            hipLaunchKernelGGL((k_resolve<kShaderWhitted, true>), dim3(grid), dim3(256), 0, st, s, lv, nx, counters, level, a, dead);
+        if (multi)
+            hipLaunchKernelGGL(k_resolve_textures<kShaderWhitted>, dim3(grid), dim3(256), 0, st, s, lv, nx, counters, level, a, dead, texLevels);
+        else if (tex)
+            hipLaunchKernelGGL((k_resolve<kShaderWhitted, 1>), dim3(grid), dim3(256), 0, st, s, lv, nx, counters, level, a, dead);
         else
-            hipLaunchKernelGGL((k_resolve<kShaderWhitted, false>), dim3(grid), dim3(256), 0, st, s, lv, nx, counters, level, a, dead);
+            hipLaunchKernelGGL((k_resolve<kShaderWhitted, 0>), dim3(grid), dim3(256), 0, st, s, lv, nx, counters, level, a, dead);
     }  // single-level shaders: k_shade_simple wrote the final results
 }
 
@@ -1558,13 +1634,14 @@ void launchResolve(int shader, const DScene& s, const Level& lv, const Level& nx
 // records are never written or re-read.  The same resolveValue and incrementalAvg on the same
 // inputs: the same bits.  (A thread per slot resolving its samples one after another measured
 // slower, C4 13.65 -> 13.78 ms: four dependent gather chains per thread.)
-template <int kShader, bool kTex, bool kViews>
-__global__ __launch_bounds__(256) void k_resolve_accumulate(DScene s, Level lv, Level nx, ShadeArgs sa, int deadChildren,
-                                                            AccumArgs a, int32_t* bitmap, int32_t* packed) {
+template <int kShader, int kTex, bool kViews>
+__device__ __forceinline__ void resolveAccumulate(const DScene& s, const Level& lv, const Level& nx, const ShadeArgs& sa,
+                                                  int deadChildren, const AccumArgs& a, int32_t* bitmap, int32_t* packed,
+                                                  const TexLevel* tl) {
     const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
     const int n = a.nSlots * a.spp;
     float4 r = make_float4(0.0F, 0.0F, 0.0F, 0.0F);
-    if (i < n) r = resolveValue<kShader, kTex, false>(s, lv, nx, i, 1, sa, deadChildren, lv.vtx[i]);
+    if (i < n) r = resolveValue<kShader, kTex, false>(s, lv, nx, i, 1, sa, deadChildren, lv.vtx[i], tl);
     const int k = i % a.spp;  // this path's sample; lanes i - k .. i - k + spp - 1 hold its slot's
     int32_t c = 0;
     for (int j = 0; j < a.spp; ++j) {  // (wave-uniform trip count)
@@ -1585,29 +1662,57 @@ __global__ __launch_bounds__(256) void k_resolve_accumulate(DScene s, Level lv, 
     }
 }
 
+template <int kShader, int kTex, bool kViews>
+__global__ __launch_bounds__(256) void k_resolve_accumulate(DScene s, Level lv, Level nx, ShadeArgs sa, int deadChildren,
+                                                            AccumArgs a, int32_t* bitmap, int32_t* packed) {
+    resolveAccumulate<kShader, kTex, kViews>(s, lv, nx, sa, deadChildren, a, bitmap, packed, nullptr);
+}
+
+// ... of a scene with several textured materials (tl: the table of levels)
+template <int kShader, bool kViews>
+__global__ __launch_bounds__(256) void k_resolve_accumulate_textures(DScene s, Level lv, Level nx, ShadeArgs sa,
+                                                                     int deadChildren, AccumArgs a, int32_t* bitmap,
+                                                                     int32_t* packed, const TexLevel* tl) {
+    resolveAccumulate<kShader, 2, kViews>(s, lv, nx, sa, deadChildren, a, bitmap, packed, tl);
+}
+
 bool launchResolveAccumulate(int shader, const DScene& s, const Level& lv, const Level& nx, const ShadeArgs& sa,
-                             bool deadChildren, const AccumArgs& a, int32_t* bitmap, int32_t* packed, hipStream_t st) {
+                             bool deadChildren, const AccumArgs& a, int32_t* bitmap, int32_t* packed, hipStream_t st,
+                             const TexLevel* texLevels) {
     if (a.spp <= 0 || 64 % a.spp != 0) return false;  // a slot's samples must share a wave
     const int dead = deadChildren ? 1 : 0;
     const int blocks = std::max(1, (a.nSlots * a.spp + 255) / 256);
 #define MRT_LAUNCH_RA_ONE(SH, TEX, VIEWS)                                                                       \
     hipLaunchKernelGGL((k_resolve_accumulate<SH, TEX, VIEWS>), dim3(blocks), dim3(256), 0, st, s, lv, nx, sa, dead, \
                        a, bitmap, packed)
+#define MRT_LAUNCH_RA_MULTI(SH, VIEWS)                                                                            \
+    hipLaunchKernelGGL((k_resolve_accumulate_textures<SH, VIEWS>), dim3(blocks), dim3(256), 0, st, s, lv, nx, sa, dead, \
+                       a, bitmap, packed, texLevels)
 #define MRT_LAUNCH_RA(SH, TEX)                               \
     do {                                                     \
         if (a.viewSlots > 0) MRT_LAUNCH_RA_ONE(SH, TEX, true); \
         else MRT_LAUNCH_RA_ONE(SH, TEX, false);              \
     } while (0)
+#define MRT_LAUNCH_RA_TEXTURES(SH)                            \
+    do {                                                     \
+        if (a.viewSlots > 0) MRT_LAUNCH_RA_MULTI(SH, true);  \
+        else MRT_LAUNCH_RA_MULTI(SH, false);                 \
+    } while (0)
     const bool tex = s.textured != 0;
+    const bool multi = s.textured > 1 && texLevels != nullptr;  // several textured materials
     if (shader == kShaderPathTracer) {
-        if (tex) MRT_LAUNCH_RA(kShaderPathTracer, true);
-        else MRT_LAUNCH_RA(kShaderPathTracer, false);
+        if (multi) MRT_LAUNCH_RA_TEXTURES(kShaderPathTracer);
+        else if (tex) MRT_LAUNCH_RA(kShaderPathTracer, 1);
+        else MRT_LAUNCH_RA(kShaderPathTracer, 0);
     } else if (shader == kShaderWhitted) {
-        if (tex) MRT_LAUNCH_RA(kShaderWhitted, true);
-        else MRT_LAUNCH_RA(kShaderWhitted, false);
+        if (multi) MRT_LAUNCH_RA_TEXTURES(kShaderWhitted);
+        else if (tex) MRT_LAUNCH_RA(kShaderWhitted, 1);
+        else MRT_LAUNCH_RA(kShaderWhitted, 0);
     } else {
         return false;
     }
+#undef MRT_LAUNCH_RA_TEXTURES
+#undef MRT_LAUNCH_RA_MULTI
 #undef MRT_LAUNCH_RA
 #undef MRT_LAUNCH_RA_ONE
     return true;

@@ -115,6 +115,16 @@ struct Level {
     int shadowSegCap;
 };
 
+// Scenes with several textured materials: one entry per level (index = level) of the records the Kd
+// replay walks (k_resolve_textures, searchLastWrite), in device memory; cap 0: no such level.
+struct TexLevel {
+    const int4* vtx;
+    const float4* kd;
+    const float4* last;
+    int cap;
+    int pad;
+};
+
 // Work units: rectangles of pixels (a reference tile cut into 8-row bands).  prefix[u] is
 // the first pixel slot of unit u; slots inside a unit are column-major.
 struct PixelMap {
@@ -229,12 +239,16 @@ void launchShade(int shader, const DScene& s, const Level& lv, const Level& nx, 
                  const RaygenArgs* regen = nullptr);
 // deadChildren: level + 1 is the depth-capped last level, whose results are all zero; its
 // records are then not read (a zero child adds exactly nothing, section 3 of DESIGN.md)
+// texLevels: the device table of levels (TexLevel) of a scene with several textured materials
+// (DScene::textured > 1); null: the single-material replay
 void launchResolve(int shader, const DScene& s, const Level& lv, const Level& nx, int* counters, int level,
-                   const ShadeArgs& a, int grid, hipStream_t st, bool deadChildren = false);
+                   const ShadeArgs& a, int grid, hipStream_t st, bool deadChildren = false,
+                   const TexLevel* texLevels = nullptr);
 void launchAccumulate(const AccumArgs& a, const float4* res, int32_t* bitmap, int32_t* packed, hipStream_t st);
 // level 1's resolve and the accumulation in one launch (Whitted / PathTracer; false: not launched)
 bool launchResolveAccumulate(int shader, const DScene& s, const Level& lv, const Level& nx, const ShadeArgs& sa,
-                             bool deadChildren, const AccumArgs& a, int32_t* bitmap, int32_t* packed, hipStream_t st);
+                             bool deadChildren, const AccumArgs& a, int32_t* bitmap, int32_t* packed, hipStream_t st,
+                             const TexLevel* texLevels = nullptr);
 // rank 0's frame assembly: up to kUnpackRanks shards per launch (rank first + k reads row first + k
 // of the gathered array, stride entries apart)
 constexpr int kUnpackRanks = 16;

@@ -341,6 +341,7 @@ struct mrt_renderer {
     // The wavefront queues of one chunk of pixel slots, and the two streams it runs on.
     struct Pipe {
         mrt::Level levels[mrt::kMaxLevels]{};
+        mrt::TexLevel* texLevels = nullptr;  // several textured materials: the levels' replay records (device)
         int* counters = nullptr;
         unsigned long long* stats = nullptr;
         int2* gstack = nullptr;        // spill stacks of the closest-hit kernel ...
@@ -644,7 +645,8 @@ void uploadScene(mrt_renderer* r, mrt::HScene& sc) {
     v.clear();
     // textures: triangle texture coordinates, texture table and texels (textured scenes only)
     d.textured = 0;
-    for (const HMaterial& m : sc.materials) d.textured |= (m.texId >= 0 && !sc.textures.empty()) ? 1 : 0;
+    // (a count: with more than one textured material the resolves take k_resolve_textures)
+    for (const HMaterial& m : sc.materials) d.textured += (m.texId >= 0 && !sc.textures.empty()) ? 1 : 0;
     if (d.textured != 0) {
         for (const HTriangle& t : sc.triangles) {
             v.push_back(make_float4(t.tA.x, t.tA.y, t.tB.x, t.tB.y));
@@ -824,6 +826,14 @@ void allocQueues(mrt_renderer* r) {
         const bool tex = real && r->ds.textured != 0;
         lv.kd = tex ? r->queueMem.alloc<float4>(cap) : nullptr;
         lv.last = tex ? r->queueMem.alloc<float4>(cap) : nullptr;
+    }
+    pp.texLevels = nullptr;
+    if (r->ds.textured > 1) {
+        TexLevel table[kMaxLevels] = {};
+        for (int l = 1; l <= nLevels && l < kMaxLevels; ++l)
+            table[l] = TexLevel{pp.levels[l].vtx, pp.levels[l].kd, pp.levels[l].last, pp.levels[l].cap, 0};
+        pp.texLevels = r->queueMem.alloc<TexLevel>(kMaxLevels);
+        MRT_HIP(hipMemcpy(pp.texLevels, table, sizeof(table), hipMemcpyHostToDevice));
     }
     pp.counters = r->queueMem.alloc<int>(kNumCounters);
     pp.stats = r->queueMem.alloc<unsigned long long>(kNumStats + kWaveLogEntries);
@@ -1164,13 +1174,14 @@ void renderPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t
         const bool resolveAcc = r->resolveAcc != 0 && topResolve >= 1;
         for (int l = topResolve; l >= (resolveAcc ? 2 : 1); --l) {
             launchResolve(shader, r->ds, pp.levels[l], pp.levels[l + 1], pp.counters, l, sa, r->workGrid, st,
-                          skipLastShade && l == nLevels - 1);
+                          skipLastShade && l == nLevels - 1, pp.texLevels);
         }
         if (!resolveAcc || !launchResolveAccumulate(shader, r->ds, pp.levels[1], pp.levels[2], sa,
-                                                    skipLastShade && 1 == nLevels - 1, aa, dBitmap, dPacked, st)) {
+                                                    skipLastShade && 1 == nLevels - 1, aa, dBitmap, dPacked, st,
+                                                    pp.texLevels)) {
             if (resolveAcc)  // (single-level shaders: nothing to resolve)
                 launchResolve(shader, r->ds, pp.levels[1], pp.levels[2], pp.counters, 1, sa, r->workGrid, st,
-                              skipLastShade && 1 == nLevels - 1);
+                              skipLastShade && 1 == nLevels - 1, pp.texLevels);
             launchAccumulate(aa, pp.levels[1].res, dBitmap, dPacked, st);
         }
         // the statistics so far into the pinned host block, the counters reset; after the last chunk
