@@ -331,7 +331,9 @@ int mrt_render_views_device(mrt_renderer *r, const mrt_view *views, int32_t nVie
  * key 37 = byte budget of the wavefront queues in MiB (0, default: half of the device memory free
  *          when they are allocated); a plan that exceeds it renders in more, smaller chunks,
  * key 38 = the first allocation's capacity of a level deeper than 1, percent of level 1 (default 200),
- * key 39 = fixed slack slots of every queue segment (default 3072).
+ * key 39 = fixed slack slots of every queue segment (default 3072),
+ * key 40 = read-only (mrt_get_tuning; mrt_set_tuning refuses it): the stack entries the scene's trees
+ *          ask of the walks (mrt_walk_stack); key 16 is on at load exactly when it is <= 128.
  *          Keys 37-39 reallocate the queues from the next frame and forget the learned plan; 38 and
  *          39 let a test reach the replan path at small frame sizes.
  * (Keys 4, 12-15, 18, 19-25, 29, 30, 32, 36 - binned emission, queue sorting, graph replay, the tile
@@ -356,6 +358,16 @@ int64_t mrt_triangle_bvh(const mrt_config *cfg, float *boxes, int32_t *offsets, 
  * root[2]), grid[6] (origin xyz, step xyz) and
  * root[3] (reference, triangles, W). */
 int64_t mrt_walk_tree(const mrt_config *cfg, uint32_t *nodes, float *grid, int32_t *root);
+/* Host only: what the scene's trees ask of the walks' stacks, as the renderer works it out at load.
+ * Fills out[6]: the stack need in entries (what mrt_get_tuning key 40 reports; the packet walk,
+ * tuning key 16, serves needs up to 128), whether the walk tree is quantized (0: a box or the grid
+ * is not finite, and every ray walks the reference tree), the depth of the reference tree, of the
+ * binary walk tree and of the wide walk tree, and the entries of a thread's spill area.  0 or -1. */
+int mrt_walk_stack(const mrt_config *cfg, int32_t *out);
+/* Host only: the bytes of the two spill areas (closest-hit and any-hit walk) of `threads` resident
+ * walk threads for a stack need, or -1 (mrt_last_error) where a renderer refuses the scene at load:
+ * the areas' 32-bit offsets would pass 2^31, or they exceed availBytes (<= 0: not checked). */
+int64_t mrt_plan_spill(int64_t threads, int32_t stackNeed, int64_t availBytes);
 /* Host only: the RegularGrid accelerator's build (RegularGrid.hpp:112-289, gridSize 32) for one
  * primitive kind of the scene cfg names (kind 0 planes, 1 spheres, 2 triangles).  Returns the
  * total list length L or -1; with non-NULL outputs fills world[12] (min xyz, max xyz, cellSize

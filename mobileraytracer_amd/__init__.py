@@ -363,6 +363,29 @@ def walk_tree(config: Config):
     return nodes, grid, root
 
 
+def walk_stack(config: Config) -> dict:
+    """Host only (mrt_walk_stack): what the configured scene's trees ask of the walks' stacks, as the
+    renderer works it out at load.  ``need``: stack entries (``Renderer.get_tuning(40)``; the packet
+    walk serves up to 128), ``quantized``: False where a box or the grid is not finite and every ray
+    walks the reference tree, ``refDepth`` / ``walkDepth`` / ``wideDepth``: levels of the reference
+    tree, the binary walk tree and the wide walk tree, ``spillDepth``: entries of a thread's spill area."""
+    out = np.zeros(6, np.int32)
+    c = config.to_c()
+    _native.check(_native.lib().mrt_walk_stack(ctypes.byref(c), _ptr(out)))
+    return {"need": int(out[0]), "quantized": bool(out[1]), "refDepth": int(out[2]), "walkDepth": int(out[3]),
+            "wideDepth": int(out[4]), "spillDepth": int(out[5])}
+
+
+def plan_spill(threads: int, stack_need: int, avail_bytes: int = 0) -> int:
+    """Host only (mrt_plan_spill): the bytes of the walks' two spill areas for ``threads`` resident
+    walk threads and a stack need.  Raises RuntimeError where a renderer refuses the scene at load:
+    the areas' 32-bit offsets would pass 2^31, or they exceed ``avail_bytes`` (0: not checked)."""
+    n = _native.lib().mrt_plan_spill(int(threads), int(stack_need), int(avail_bytes))
+    if n < 0:
+        raise RuntimeError(_native.lib().mrt_last_error().decode())
+    return int(n)
+
+
 def triangle_bvh(config: Config):
     """Host-side triangle BVH of the configured scene (no GPU): boxes (N, 6), offsets, counts,
     order - the layout of the reference's BVHNode array (BVH.hpp:56-60)."""

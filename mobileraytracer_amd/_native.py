@@ -26,7 +26,7 @@ EXPORTED_SYMBOLS = (
     "mrt_android_time_renderer", "mrt_android_sample", "mrt_android_number_of_lights", "mrt_android_resize",
     "mrt_android_vertices", "mrt_android_colors", "mrt_android_camera", "mrt_android_reset",
     "mrt_get_queue_info", "mrt_plan_queues", "mrt_render_views", "mrt_render_views_device",
-    "mrt_kat_accumulate", "mrt_cast_rays_device",
+    "mrt_kat_accumulate", "mrt_cast_rays_device", "mrt_walk_stack", "mrt_plan_spill",
     "RayTrace", "stopRender",
 )
 
@@ -166,6 +166,8 @@ def load_library(path=LIB_PATH):
         "mrt_get_tuning": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
         "mrt_triangle_bvh": (ctypes.c_int64, [vp, vp, vp, vp, vp]),
         "mrt_walk_tree": (ctypes.c_int64, [vp, vp, vp, vp]),
+        "mrt_walk_stack": (ctypes.c_int, [vp, vp]),
+        "mrt_plan_spill": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64]),
         "mrt_decode_texture": (ctypes.c_int64, [ctypes.c_char_p, vp, vp]),
         "mrt_regular_grid": (ctypes.c_int64, [vp, ctypes.c_int32, vp, vp, vp]),
         "mrt_grid_box_test": (ctypes.c_int, [ctypes.c_int32, vp, vp]),

@@ -259,7 +259,14 @@ __device__ __forceinline__ bool leafTriangles(const DScene& s, int first, int co
         if (!triTest(ld4(g), ld4(g + 1), ld4(g + 2), o, d, &t, &u, &v)) continue;
         if (t < kEpsilon) continue;
         if (kAny) {
-            if (!(t >= b->t)) return true;
+            // accepted (Triangle.cpp:104: neither t < eps nor t >= length), then BVH.hpp:348-352: the
+            // walk ends where the accepted length is below the one before.  A NaN t (a non-finite
+            // triangle) is accepted and ends nothing; it stays as the length the next test sees.
+            if (!(t >= b->t)) {
+                const float last = b->t;
+                b->t = t;
+                if (t < last) return true;
+            }
         } else if (kTies ? better(t, code, *b) : !(t >= b->t)) {
             b->t = t;
             b->u = u;
@@ -498,6 +505,9 @@ __device__ __forceinline__ Best closestHit(const DScene& s, v3 o, v3 d, uint32_t
             b.code = code;
         }
     }
+    // Shader.cpp:122: a hit only where the length fell below the ray's; after a NaN t (accepted as any
+    // other, leafTriangles) it need not have
+    if (!(b.t < kRayLengthMax)) b.code = kNoPrim;
     return b;
 }
 
@@ -509,7 +519,8 @@ __device__ __forceinline__ bool anyHit(const DScene& s, v3 o, v3 d, uint32_t src
     Best b{dist, 0.0F, 0.0F, kNoPrim};
     if (traverse<kPlane, true>(s, s.planeNodes, s.planeRoot, o, d, inv, src, &b, st, cnt)) return true;
     if (traverse<kSphere, true>(s, s.sphereNodes, s.sphereRoot, o, d, inv, src, &b, st, cnt)) return true;
-    return traverse<kTriangle, true>(s, s.triNodes, s.triRootRef, o, d, inv, src, &b, st, cnt);
+    if (traverse<kTriangle, true>(s, s.triNodes, s.triRootRef, o, d, inv, src, &b, st, cnt)) return true;
+    return b.t < dist;  // Shader.cpp:156 (the length changes without ending the walk only after a NaN t)
 }
 
 }  // namespace mrt

@@ -432,7 +432,7 @@ __global__ __launch_bounds__(256) void k_trace_other(DScene s, Level lv, int* co
                        gridWalk<kTriangle, kAny>(s, s.triGrid, o, d, src, &b);
         }
         if (kAny) {
-            lv.sC[i].w = occluded ? 1.0F : 0.0F;
+            lv.sC[i].w = (occluded || b.t < d4.w) ? 1.0F : 0.0F;  // (Shader.cpp:156; see anyHit)
             continue;
         }
         for (int j = 0; j < s.nLights; ++j) {  // Shader.cpp:166-171
@@ -445,6 +445,7 @@ __global__ __launch_bounds__(256) void k_trace_other(DScene s, Level lv, int* co
             const uint32_t code = encodePrim(kLight, static_cast<uint32_t>(j));
             if (betterThan(t, code, b.t, b.code)) b = Best{t, u, v, code};
         }
+        if (!(b.t < kRayLengthMax)) b.code = kNoPrim;  // Shader.cpp:122 (see closestHit)
         lv.hit[i] = make_float4(b.t, b.u, b.v, bitsf(b.code));
     }
 }
@@ -1468,9 +1469,18 @@ int persistentGrid(K kernel, int slot, int maxThreads) {
         else                                                                                                   \
             hipLaunchKernelGGL((KERNEL<false, V, C>), dim3(g), dim3(kWalkThreads), 0, st, s, lv, counters, level, gstack, gdepth, stats); \
     } while (0)
+// A scene without a quantized walk tree (DScene::qEnabled == 0: a box or the grid is not finite) holds
+// triangles whose test can return a NaN t.  The reference accepts such a hit (Triangle.cpp:104 rejects
+// t < eps and t >= length, both false for NaN), after which every later candidate passes the
+// t >= length test: its answer then depends on the order of its own walk, and the ray counts as a
+// miss where the last accepted t is NaN (Shader.cpp:122).  Only the per-wave reference walk
+// (variant 0: closestHit / anyHit of mrt_device.hpp) visits in that order, so it serves every ray of
+// such a scene, whatever the walk, cull, packet and fusion keys say.
+static bool referenceOrderOnly(const DScene& s) { return s.qEnabled == 0; }
+
 #define MRT_LAUNCH_WALK(KERNEL, SLOT)                                                                           \
     do {                                                                                                       \
-        if (s.variant == 0) MRT_LAUNCH_ONE(KERNEL, 0, kCullNone, SLOT);                                        \
+        if (s.variant == 0 || referenceOrderOnly(s)) MRT_LAUNCH_ONE(KERNEL, 0, kCullNone, SLOT);               \
         else if (s.cull == kCullFast) MRT_LAUNCH_ONE(KERNEL, 1, kCullFast, SLOT + 1);                          \
         else if (s.cull == kCullCertified) MRT_LAUNCH_ONE(KERNEL, 1, kCullCertified, SLOT + 2);                \
         else if (s.cull == kCullExact) MRT_LAUNCH_ONE(KERNEL, 1, kCullExact, SLOT + 4);                        \
@@ -1478,7 +1488,8 @@ int persistentGrid(K kernel, int slot, int maxThreads) {
     } while (0)
 
 bool packetLevel1(const DScene& s) {
-    return s.accel == kAccBVH && s.packet != 0 && s.variant == 1 && (s.cull == kCullNone || s.cull == kCullExact);
+    return s.accel == kAccBVH && s.packet != 0 && s.variant == 1 && (s.cull == kCullNone || s.cull == kCullExact) &&
+           !referenceOrderOnly(s);
 }
 
 void launchTrace(const DScene& s, const Level& lv, int* counters, int level, int2* gstack, int gdepth,
@@ -1528,8 +1539,7 @@ void launchShadow(const DScene& s, const Level& lv, int* counters, int level, in
 }
 
 bool canFuseLevel1(int shader, const DScene& s, const ShadeArgs& a) {
-    return s.fuseShade != 0 && s.accel == kAccBVH && s.packet != 0 && s.variant == 1 &&
-           (s.cull == kCullNone || s.cull == kCullExact) && (shader == kShaderWhitted || shader == kShaderPathTracer) &&
+    return s.fuseShade != 0 && packetLevel1(s) && (shader == kShaderWhitted || shader == kShaderPathTracer) &&
            s.textured == 0 && a.stats == nullptr && s.leanShade != 0;
 }
 

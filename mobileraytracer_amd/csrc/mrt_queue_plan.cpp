@@ -148,6 +148,26 @@ int64_t planRaySlotBytes(bool textured) {
 
 int64_t planShadowSlotBytes() { return 3 * 16; }  // sO, sD, sC: float4
 
+int64_t planSpillBytes(int64_t threads, int64_t gdepth, int64_t availBytes, std::string* err) {
+    if (threads < 1 || gdepth < 1 || threads > (int64_t{1} << 31) || gdepth > (int64_t{1} << 24)) {
+        *err = "spill stacks: threads 1 .. 2^31, depth 1 .. 2^24";
+        return -1;
+    }
+    // the end of the last thread's area in words: every index gofs + sp - depth stays an int
+    if (threads * gdepth * 2 > (int64_t{1} << 31) - 1) {
+        *err = "the scene's tree is too deep for the walks' spill stacks: " + std::to_string(threads) + " threads x " +
+               std::to_string(gdepth) + " entries pass the 32-bit offsets";
+        return -1;
+    }
+    const int64_t bytes = 2 * threads * gdepth * 8;
+    if (availBytes > 0 && bytes > availBytes) {
+        *err = "the scene's tree is too deep for the device memory: the walks' spill stacks need " +
+               std::to_string(bytes) + " bytes beside the queues, " + std::to_string(availBytes) + " are left";
+        return -1;
+    }
+    return bytes;
+}
+
 bool planQueues(const mrt_queue_plan_request& q, mrt_queue_plan* out, std::string* err) {
     Params p{};
     p.levels = q.levels;

@@ -30,4 +30,11 @@ int64_t planShadowSlotBytes();
 // slot fits the byte budget (for the worst-case plan: "one pixel's worst-case ray tree ...").
 bool planQueues(const mrt_queue_plan_request& q, mrt_queue_plan* out, std::string* err);
 
+// The per-lane walks' spill stacks, which the plans above do not count: two areas (the closest-hit
+// and the any-hit walk's, which run together) of `threads` x `gdepth` entries of 8 bytes, thread k's
+// at the 32-bit offset k * gdepth * 2 (in 4-byte words: makeRefStack).  Returns their bytes, or -1
+// with *err set where the last thread's area would end past 2^31 words or the two areas exceed
+// `availBytes` (what the device has left beside the queues; <= 0: not checked).
+int64_t planSpillBytes(int64_t threads, int64_t gdepth, int64_t availBytes, std::string* err);
+
 }  // namespace mrt

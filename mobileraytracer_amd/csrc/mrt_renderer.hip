@@ -190,6 +190,30 @@ int bvhDepth(const std::vector<mrt::HBVHNode>& nodes) {
     return best;
 }
 
+// Levels of the quantized wide walk tree (0: not quantized, no triangle, or a leaf root).
+int wideDepth(bool quantized, const mrt::GRoot& root, const std::vector<mrt::QNode4>& qn) {
+    int depth4 = 0;
+    std::vector<std::pair<int32_t, int>> w;
+    if (quantized && root.count > 0 && root.ref >= 0) w.push_back({root.ref, 1});
+    while (!w.empty()) {
+        const auto [i, dep] = w.back();
+        w.pop_back();
+        depth4 = std::max(depth4, dep);
+        for (int32_t c : qn[static_cast<size_t>(i)].ref)
+            if (c >= 0 && c != mrt::kEmptyChild) w.push_back({c, dep + 1});
+    }
+    return depth4;
+}
+
+// Worst-case traversal stack entries over all node layouts: a binary tree's walks hold one entry
+// per level; a visit of the wide tree pushes up to kWalkWidth - 1 entries, that many per level.
+int walkStackNeed(int binaryDepth, int depth4) {
+    return std::max(binaryDepth + 2, (mrt::kWalkWidth - 1) * depth4 + 2);
+}
+
+// Entries of a thread's spill area: what the need exceeds the LDS stack by.
+int spillDepth(int stackNeed) { return std::max(1, stackNeed - mrt::kLdsStackMin); }
+
 float4 f4(mrt::v3 v, float w) { return make_float4(v.x, v.y, v.z, w); }
 float asFloat(int32_t i) {
     float f;
@@ -547,7 +571,6 @@ void uploadScene(mrt_renderer* r, mrt::HScene& sc) {
     r->nTriNodes = static_cast<int64_t>(tn.size());
     r->triDepth = std::max(bvhDepth(tn), bvhDepth(wn));
     r->maxBvhDepth = std::max({r->triDepth, bvhDepth(pn), bvhDepth(sn)});
-    r->stackNeed = r->maxBvhDepth + 2;
 
     if (r->keepHost) {
         r->hostTris = sc.triangles;  // BVH order, as Shader::getTriangles returns them
@@ -582,19 +605,12 @@ void uploadScene(mrt_renderer* r, mrt::HScene& sc) {
         }
         d.triQNodesF = r->sceneMem.upload(qf, st);
     }
-    // a visit pushes up to kWalkWidth - 1 entries: the walk's stack holds that many per level
+    r->stackNeed = walkStackNeed(r->maxBvhDepth, wideDepth(d.qEnabled != 0, d.triRoot, qn));
+    // the spill stacks' 32-bit offsets over this device's resident walk threads (whether the areas
+    // fit the device memory is checked where they are allocated, adoptPlan)
     {
-        int depth4 = 0;
-        std::vector<std::pair<int32_t, int>> w;
-        if (d.qEnabled != 0 && d.triRoot.count > 0 && d.triRoot.ref >= 0) w.push_back({d.triRoot.ref, 1});
-        while (!w.empty()) {
-            const auto [i, dep] = w.back();
-            w.pop_back();
-            depth4 = std::max(depth4, dep);
-            for (int32_t c : qn[static_cast<size_t>(i)].ref)
-                if (c >= 0 && c != kEmptyChild) w.push_back({c, dep + 1});
-        }
-        r->stackNeed = std::max(r->stackNeed, (kWalkWidth - 1) * depth4 + 2);
+        std::string err;
+        if (planSpillBytes(r->traceThreads, spillDepth(r->stackNeed), 0, &err) < 0) throw std::runtime_error(err);
     }
     toDeviceBVH(tn, sc.triangles.size(), &g, &d.triRootRef, 0, nullptr, &conesRef);
     {
@@ -791,7 +807,7 @@ void allocQueues(mrt_renderer* r) {
     r->queueMem.release();
     r->chunkSlots = static_cast<int>(r->plan.chunkSlots);
     const int nLevels = r->nLevels;
-    r->gdepth = std::max(1, r->stackNeed - kLdsStackMin);
+    r->gdepth = spillDepth(r->stackNeed);
     mrt_renderer::Pipe& pp = r->pipe;
     // Ray / hit / payload buffers of levels L and L+2 are never live together (level L's rays are
     // dead once k_shade(L) has read them; its vertex and result records stay until the resolve),
@@ -927,6 +943,15 @@ void adoptPlan(mrt_renderer* r, mrt_queue_plan_request q) {
         if (q.worstCase != 0) throw std::runtime_error(err);
         q.worstCase = 1;
         if (!mrt::planQueues(q, &plan, &err)) throw std::runtime_error(err);
+    }
+    {
+        // the spill stacks are allocated beside the queues: what the device has left for them
+        size_t freeBytes = 0, totalBytes = 0;
+        MRT_HIP(hipMemGetInfo(&freeBytes, &totalBytes));
+        const int64_t left = static_cast<int64_t>((freeBytes + r->queueMem.total) / static_cast<size_t>(std::max(1, r->deviceShare))) -
+                             plan.bytes;
+        if (mrt::planSpillBytes(r->traceThreads, spillDepth(r->stackNeed), std::max<int64_t>(1, left), &err) < 0)
+            throw std::runtime_error(err);
     }
     r->plan = plan;
     r->planBudget = q.byteBudget;
@@ -2246,6 +2271,52 @@ int64_t mrt_walk_tree(const mrt_config* cfg, uint32_t* nodes, float* grid, int32
     return rc == 0 ? n : -1;
 }
 
+int mrt_walk_stack(const mrt_config* cfg, int32_t* out) {
+    using namespace mrt;
+    return guarded([&] {
+        HScene sc;
+        const float ratio = cfg->height > 0 ? static_cast<float>(cfg->width) / static_cast<float>(cfg->height) : 1.0F;
+        GCamera cam{};
+        if (cfg->sceneIndex >= 0 && cfg->sceneIndex <= 3) {
+            sc = builtinScene(cfg->sceneIndex);
+            cam = builtinCamera(cfg->sceneIndex, ratio);
+        } else {
+            std::string err;
+            if (!loadObjScene(cfg->objFilePath ? cfg->objFilePath : "", cfg->mtlFilePath ? cfg->mtlFilePath : "", &sc,
+                              &err))
+                throw std::runtime_error(err);
+            if (!loadCameraFile(cfg->camFilePath ? cfg->camFilePath : "", ratio, &cam, &err)) throw std::runtime_error(err);
+        }
+        // the trees of uploadScene, in its order
+        std::vector<int32_t> perm;
+        const int otherDepth = std::max(bvhDepth(buildBVH(&sc.planes, &perm)), bvhDepth(buildBVH(&sc.spheres, &perm)));
+        const std::vector<HBVHNode> tn = buildBVH(&sc.triangles, &perm);
+        const int maxDepth = cfg->maxDepth > 0 ? cfg->maxDepth : kRayDepthMaxDefault;
+        std::vector<double> cost;
+        const std::vector<HBVHNode> wn = frameWalkTree(walkTreeOver(tn), sc, cam, cfg->width, cfg->height, maxDepth, &cost);
+        GRoot root{};
+        QGrid g{};
+        std::vector<QNode4> qn;
+        int top = 0;
+        const bool quantized = toQuantizedBVH4(wn, sc.triangles.size(), &root, kTopNodesMax, &top, &g, &qn, nullptr,
+                                               cost.empty() ? nullptr : &cost);
+        const int depth4 = wideDepth(quantized, root, qn);
+        out[0] = walkStackNeed(std::max({bvhDepth(tn), bvhDepth(wn), otherDepth}), depth4);
+        out[1] = quantized ? 1 : 0;
+        out[2] = bvhDepth(tn);
+        out[3] = bvhDepth(wn);
+        out[4] = depth4;
+        out[5] = spillDepth(out[0]);
+    });
+}
+
+int64_t mrt_plan_spill(int64_t threads, int32_t stackNeed, int64_t availBytes) {
+    std::string err;
+    const int64_t bytes = mrt::planSpillBytes(threads, spillDepth(stackNeed), availBytes, &err);
+    if (bytes < 0) gLastError = err;
+    return bytes;
+}
+
 int mrt_grid_box_test(int32_t kind, const float* prim, const float* box) {
     using namespace mrt;
     const HAABB b{v3{box[0], box[1], box[2]}, v3{box[3], box[4], box[5]}};
@@ -2347,6 +2418,7 @@ int mrt_get_tuning(const mrt_renderer* r, int32_t key, int32_t* value) {
         case 37: *value = r->queueBudgetMiB; return 0;
         case 38: *value = r->queueGrowthPct; return 0;
         case 39: *value = r->queueSlack; return 0;
+        case 40: *value = r->stackNeed; return 0;  // read-only: mrt_set_tuning knows no key 40
         default: break;
     }
     gLastError = "unknown tuning key";

@@ -23,10 +23,15 @@ def _leaf_key(ref):
 def test_walk_tree_holds_reference_leaves_with_margin(case, opt, monkeypatch):
     """... for the default build, without the insertion-based optimisation of the tree over the
     leaves (MOBILERT_TREE_OPT=0) and with up to 100 rounds of it."""
-    import mobileraytracer_amd as m
     if opt is not None:
         monkeypatch.setenv("MOBILERT_TREE_OPT", opt)
-    cfg = make_cfg(64, 64, **case)
+    check_walk_tree_holds_reference_leaves(make_cfg(64, 64, **case))
+
+
+def check_walk_tree_holds_reference_leaves(cfg):
+    """The two properties of the module's docstring on the host build of `cfg`'s scene (also run on
+    the generated scenes of test_tree_shapes.py)."""
+    import mobileraytracer_amd as m
     boxes, off, cnt, _ = m.triangle_bvh(cfg)
     leaves = {(int(off[i]), int(cnt[i])): boxes[i].astype(np.float64) for i in range(len(cnt)) if cnt[i] > 0}
     nodes, grid, root = m.walk_tree(cfg)
