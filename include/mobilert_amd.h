@@ -15,6 +15,8 @@
  *                             as one submission (no single reference call)
  *   mrt_cast_rays_device      Shader::rayTrace's intersection part / Shader::shadowTrace for a batch of
  *                             the caller's rays, resident in device memory (no single reference call)
+ *   mrt_shade_rays_device     Shader::rayTrace (the whole ray tree) for a batch of the caller's rays: linear
+ *                             float radiance per ray (no single reference call)
  *   mrt_stop_render           Renderer::stopRender (Renderer.cpp:93-99); JNI rtStopRender
  *   mrt_get_sample            Renderer::getSample (Renderer.cpp:177-179); JNI rtGetSample
  *   mrt_get_total_casted_rays Renderer::getTotalCastedRays (Renderer.cpp:204-207)
@@ -466,6 +468,53 @@ typedef struct mrt_ray_batch {
  * Each output may be NULL (not wanted); at least one wanted output must be non-NULL. */
 int mrt_cast_rays_device(mrt_renderer *r, const mrt_ray_batch *rays, int32_t any,
                          int32_t *d_kind, int32_t *d_index, float *d_t, void *stream);
+
+/* ---- shaded ray queries (on the GPU; beyond the reference's entry points) ----
+ * mrt_shade_rays_device: the radiance that arrives along each ray of a caller-supplied batch, as
+ * linear float RGB.  d_rgb[i] is, bit for bit, the value Shader::rayTrace (Shader.cpp:86-130) leaves
+ * in `rgb` for ray i taken as the depth-1 ray of a path whose sampler draws derive from key[i] - the
+ * value Renderer::renderScene hands to incrementalAvg (Renderer.cpp:131-160) - under the renderer's
+ * shader, accelerator, maxDepth, samplesLight, tuning and cull settings.  It is a pure function of
+ * (scene, shader, depth, samplesLight, ray, source, key): batch order, chunking and the queue plan
+ * do not change a bit.
+ *
+ * The batch runs through the frame's wavefront with level 1 fed from the caller's rays instead of
+ * the camera's: in chunks of the queue plan's level-1 paths (mrt_config.maxPathsPerPass bounds them;
+ * the plan is made for the batch, as it is re-made between frames and batches of views), an
+ * overflowed chunk redone with queues planned from its demand, exactly as a frame's pass is.  The
+ * deeper levels' queues can overflow, so the call is host-synchronous like mrt_render_frame_device:
+ * the work runs on the renderer's stream after everything enqueued on `stream` before the call, and
+ * the call returns when the radiance is written.  `src` pairs behave as in mrt_cast_rays_device.
+ * State: frames, batches of views and hit queries made afterwards have the bits and counts they would
+ * have had without the call; mrt_get_total_casted_rays, mrt_get_frame_stats and mrt_get_sample do not
+ * see a shade batch (mrt_get_queue_info reports the last pass, which may be the batch's).  After
+ * mrt_stop_render the call does nothing and returns 0, as a frame does.
+ * A device group (deviceCount > 1) is refused: -1, nothing done.  Argument errors (a NULL handle,
+ * batch, orig, dir or d_rgb, n outside 1 .. 2^31 - 1, a stride of 1, 2 or below 0 for the rays or
+ * for rgb) return -1 before any device work, with a message in mrt_last_error(); they are checked
+ * before the renderer is read. */
+
+/* host only: the path key of (pixel index y*width+x, sample), the key every sampler draw of a path derives from */
+uint32_t mrt_path_key(uint32_t pixel, uint32_t sample);
+
+typedef struct mrt_shade_batch {
+    mrt_ray_batch rays;      /* orig, dir, strides, n, src as for mrt_cast_rays_device; dist ignored */
+    const uint32_t *key;     /* device or NULL: ray i's path key; NULL: mrt_path_key((uint32_t)i, 0) */
+} mrt_shade_batch;
+
+/* d_rgb: device, ray i's radiance at d_rgb + i*rgbStride (floats; 0 means 3, else >= 3);
+ * raysOut: host or NULL: [0] rays, [1] shadow rays built for the batch (as mrt_frame_stats.rays / shadowRays) */
+int mrt_shade_rays_device(mrt_renderer *r, const mrt_shade_batch *b, float *d_rgb, int64_t rgbStride,
+                          uint64_t *raysOut, void *stream);
+
+/* the renderer's camera rays as a batch: path p = slot*spp + s in this shard's slot order, samples
+ * sampleBase .. sampleBase+spp-1 (spp <= 0: samplesPixel); view NULL: the renderer's camera and sampler.
+ * Outputs (device, each may be NULL, at least one not): orig/dir packed xyz, key, pixel (y*width+x).
+ * The rays' bits are those of the records a frame's level 1 walks; the kernel is enqueued on `stream`
+ * (NULL: the renderer's own) and the call does not wait for it.
+ * Returns the path count (pixelSlots*spp) or -1. */
+int64_t mrt_camera_rays_device(mrt_renderer *r, const mrt_view *view, int32_t sampleBase, int32_t spp,
+                               float *d_orig, float *d_dir, uint32_t *d_key, int32_t *d_pixel, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@ Python mirror of the reference's native surface for this path:
 
 Everything computes in the HIP kernels of ``libmobilert_amd.so``; there is no CPU path.
 """
+import contextlib
 import ctypes
 import dataclasses
 import threading
@@ -276,23 +277,7 @@ class Renderer:
         ValueError for a tensor that is not on the renderer's GPU or has another shape."""
         import torch
 
-        device = orig.device
-        want = self.config.device if not self.config.devices else -1
-        if not orig.is_cuda or (want >= 0 and device.index != want):
-            raise ValueError("orig: a tensor on the renderer's GPU (it is on %s)" % device)
-        n = orig.shape[0] if orig.dim() == 2 else -1
-
-        def rows(a, name):
-            """The tensor to read and its row stride in floats; never 0, which the C entry point
-            takes for 'packed' (rows 3 apart)."""
-            if a.device != device or a.dtype != torch.float32 or a.dim() != 2 or a.shape[0] != n or a.shape[1] < 3:
-                raise ValueError("%s: a float32 tensor of shape (%d, >= 3) on %s" % (name, n, device))
-            if a.stride(1) != 1 or (n > 1 and a.stride(0) < 3):
-                a = a[:, :3].contiguous()
-            return a, (a.stride(0) if n > 1 else 3)
-
-        orig, orig_stride = rows(orig, "orig")
-        dirs, dir_stride = rows(dirs, "dirs")
+        device, n, orig, orig_stride, dirs, dir_stride = self._ray_tensors(orig, dirs)
         if any_hit:
             if dist is None:
                 raise ValueError("any_hit needs dist")
@@ -308,9 +293,45 @@ class Renderer:
         t = None if any_hit else torch.empty(n, dtype=torch.float32, device=device)
         if n == 0:
             return kind if any_hit else (kind, index, t)
-        # Handle 0 would mean the renderer's own stream, which is not ordered against torch's null
-        # stream: from there the query goes through a stream of this renderer's, joined to the null
-        # stream by torch on both sides (events only; nothing waits on the host).
+        with self._query_stream_of(device) as stream:
+            self.cast_rays_device(orig.data_ptr(), dirs.data_ptr(), n, d_dist=dist.data_ptr() if any_hit else 0,
+                                  d_src=src.data_ptr() if src is not None else 0, orig_stride=orig_stride,
+                                  dir_stride=dir_stride, any_hit=any_hit, d_kind=kind.data_ptr(),
+                                  d_index=0 if any_hit else index.data_ptr(), d_t=0 if any_hit else t.data_ptr(),
+                                  stream=stream)
+        return kind if any_hit else (kind, index, t)
+
+    def _ray_tensors(self, orig, dirs):
+        """The tensor handling of cast_rays / shade_rays: (device, n, orig, orig_stride, dirs,
+        dir_stride), the strides in floats and never 0, which the C entry points take for 'packed'
+        (rows 3 apart).  ValueError for a tensor off the renderer's GPU or of another shape."""
+        import torch
+
+        device = orig.device
+        want = self.config.device if not self.config.devices else -1
+        if not orig.is_cuda or (want >= 0 and device.index != want):
+            raise ValueError("orig: a tensor on the renderer's GPU (it is on %s)" % device)
+        n = orig.shape[0] if orig.dim() == 2 else -1
+
+        def rows(a, name):
+            if a.device != device or a.dtype != torch.float32 or a.dim() != 2 or a.shape[0] != n or a.shape[1] < 3:
+                raise ValueError("%s: a float32 tensor of shape (%d, >= 3) on %s" % (name, n, device))
+            if a.stride(1) != 1 or (n > 1 and a.stride(0) < 3):
+                a = a[:, :3].contiguous()
+            return a, (a.stride(0) if n > 1 else 3)
+
+        orig, orig_stride = rows(orig, "orig")
+        dirs, dir_stride = rows(dirs, "dirs")
+        return device, n, orig, orig_stride, dirs, dir_stride
+
+    @contextlib.contextmanager
+    def _query_stream_of(self, device):
+        """The stream handle a query on torch's current stream is given.  Handle 0 would mean the
+        renderer's own stream, which is not ordered against torch's null stream: from there the query
+        goes through a stream of this renderer's, joined to the null stream by torch on both sides
+        (events only; nothing waits on the host)."""
+        import torch
+
         current = torch.cuda.current_stream(device)
         via = current
         if current.cuda_stream == 0:
@@ -319,15 +340,86 @@ class Renderer:
                 via = self._query_stream = torch.cuda.Stream(device)
             via.wait_stream(current)
         try:
-            self.cast_rays_device(orig.data_ptr(), dirs.data_ptr(), n, d_dist=dist.data_ptr() if any_hit else 0,
-                                  d_src=src.data_ptr() if src is not None else 0, orig_stride=orig_stride,
-                                  dir_stride=dir_stride, any_hit=any_hit, d_kind=kind.data_ptr(),
-                                  d_index=0 if any_hit else index.data_ptr(), d_t=0 if any_hit else t.data_ptr(),
-                                  stream=via.cuda_stream)
+            yield via.cuda_stream
         finally:
             if via is not current:
                 current.wait_stream(via)
-        return kind if any_hit else (kind, index, t)
+
+    # -- shaded ray queries --------------------------------------------------------------
+    def shade_rays_device(self, d_orig: int, d_dir: int, n: int, *, d_key: int = 0, d_src: int = 0,
+                          orig_stride: int = 3, dir_stride: int = 3, d_rgb: int, rgb_stride: int = 3,
+                          stream: int = 0):
+        """mrt_shade_rays_device: the radiance arriving along ``n`` rays resident in device memory -
+        the renderer's whole ray tree (shader, maxDepth, samplesLight) under each ray, taken as the
+        depth-1 ray of a path with key ``d_key[i]`` (0: ``path_key(i, 0)``) - as linear float RGB at
+        ``d_rgb + i * rgb_stride``.  Pointers as ints, strides in floats; ``d_src`` as for
+        cast_rays_device.  Ordered after ``stream``'s earlier work; returns, with the radiance
+        written, the (rays, shadow rays) the batch built.  Frames do not see the call."""
+        batch = _native.MrtShadeBatch(
+            _native.MrtRayBatch(d_orig or None, d_dir or None, None, d_src or None, int(orig_stride), int(dir_stride),
+                                int(n)), d_key or None)
+        rays = (ctypes.c_uint64 * 2)()
+        _native.check(self._lib.mrt_shade_rays_device(
+            self._h, ctypes.byref(batch), ctypes.c_void_p(d_rgb or None), int(rgb_stride), rays,
+            ctypes.c_void_p(stream or None)))
+        return int(rays[0]), int(rays[1])
+
+    def shade_rays(self, orig, dirs, keys=None, src=None):
+        """shade_rays_device for torch tensors on the renderer's device, with cast_rays' handling of
+        ``orig`` / ``dirs`` / ``src``; ``keys``: (n,) path keys (any integer dtype holding their 32 bits;
+        None: ``path_key(i, 0)``).  Returns the radiance, float32 (n, 3), allocated and ordered on
+        torch's current stream; an empty batch returns an empty tensor."""
+        import torch
+
+        device, n, orig, orig_stride, dirs, dir_stride = self._ray_tensors(orig, dirs)
+        if keys is not None:
+            if keys.device != device or keys.shape != (n,) or keys.dtype.is_floating_point:
+                raise ValueError("keys: an integer tensor of shape (%d,) on %s" % (n, device))
+            # the keys' 32 bits as int32 (few torch kernels take uint32; a wider dtype wraps)
+            if keys.dtype == torch.uint32:
+                keys = keys.contiguous().view(torch.int32)
+            elif keys.dtype != torch.int32:
+                keys = keys.to(torch.int64).to(torch.int32)
+            keys = keys.contiguous()
+        if src is not None:
+            if src.device != device or src.shape != (n, 2):
+                raise ValueError("src: a tensor of shape (%d, 2) on %s" % (n, device))
+            src = src.to(torch.int32).contiguous()
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=device)
+        if n == 0:
+            return rgb
+        with self._query_stream_of(device) as stream:
+            self.shade_rays_device(orig.data_ptr(), dirs.data_ptr(), n, d_key=keys.data_ptr() if keys is not None else 0,
+                                   d_src=src.data_ptr() if src is not None else 0, orig_stride=orig_stride,
+                                   dir_stride=dir_stride, d_rgb=rgb.data_ptr(), stream=stream)
+        return rgb
+
+    def camera_rays(self, camera=None, sample_base: int = 0, spp: Optional[int] = None):
+        """mrt_camera_rays_device: the renderer's camera rays as a batch for shade_rays / cast_rays -
+        (orig (n, 3), dirs (n, 3) float32, keys (n,) uint32, pixels (n,) int32) torch tensors on the
+        renderer's GPU, path ``slot * spp + s`` in this shard's slot order, samples ``sample_base ..
+        sample_base + spp - 1`` (``spp`` None: samplesPixel).  ``camera``: set_camera's tuple for
+        another view through the renderer's pixel sampler; None: the renderer's camera."""
+        import torch
+
+        spp = int(spp) if spp else max(1, self.config.samplesPixel)
+        n = self.scene_info()["pixelSlots"] * spp
+        device = torch.device("cuda", self.config.device if self.config.device >= 0 and not self.config.devices
+                              else torch.cuda.current_device())
+        orig = torch.empty((n, 3), dtype=torch.float32, device=device)
+        dirs = torch.empty((n, 3), dtype=torch.float32, device=device)
+        keys = torch.empty(n, dtype=torch.int32, device=device).view(torch.uint32)
+        pixels = torch.empty(n, dtype=torch.int32, device=device)
+        if n == 0:
+            return orig, dirs, keys, pixels
+        view = self._views([camera]) if camera is not None else None
+        got = self._lib.mrt_camera_rays_device(self._h, view, int(sample_base), spp, orig.data_ptr(), dirs.data_ptr(),
+                                               keys.data_ptr(), pixels.data_ptr(),
+                                               ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream or None))
+        if got != n:
+            _native.check(-1 if got < 0 else 0)
+            raise RuntimeError("mrt_camera_rays_device returned %d paths, %d expected" % (got, n))
+        return orig, dirs, keys, pixels
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -569,6 +661,12 @@ def ray_trace(config: Config, async_: bool = False):
         return th
     work()
     return None
+
+
+def path_key(pixel: int, sample: int) -> int:
+    """mrt_path_key (host only): the key every sampler draw of the path of (pixel index y * width + x,
+    sample) derives from - what shade_rays takes as ``keys``."""
+    return int(_native.lib().mrt_path_key(int(pixel) & 0xFFFFFFFF, int(sample) & 0xFFFFFFFF))
 
 
 def stop_render():

@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = (
     "mrt_android_vertices", "mrt_android_colors", "mrt_android_camera", "mrt_android_reset",
     "mrt_get_queue_info", "mrt_plan_queues", "mrt_render_views", "mrt_render_views_device",
     "mrt_kat_accumulate", "mrt_cast_rays_device", "mrt_walk_stack", "mrt_plan_spill",
+    "mrt_path_key", "mrt_shade_rays_device", "mrt_camera_rays_device",
     "RayTrace", "stopRender",
 )
 
@@ -62,6 +63,10 @@ class MrtView(ctypes.Structure):  # mrt_view: the arguments of mrt_set_camera
 class MrtRayBatch(ctypes.Structure):  # mrt_ray_batch: a device-resident batch of rays (mrt_cast_rays_device)
     _fields_ = [("orig", ctypes.c_void_p), ("dir", ctypes.c_void_p), ("dist", ctypes.c_void_p), ("src", ctypes.c_void_p),
                 ("origStride", ctypes.c_int64), ("dirStride", ctypes.c_int64), ("n", ctypes.c_int64)]
+
+
+class MrtShadeBatch(ctypes.Structure):  # mrt_shade_batch: rays and their path keys (mrt_shade_rays_device)
+    _fields_ = [("rays", MrtRayBatch), ("key", ctypes.c_void_p)]
 
 
 class MrtSceneInfo(ctypes.Structure):
@@ -202,6 +207,9 @@ def load_library(path=LIB_PATH):
         "mrt_kat_accumulate": (ctypes.c_int, [vp] + [ctypes.c_int32] * 6 + [vp, P(ctypes.c_int32)]),
         "mrt_trace_rays": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]),
         "mrt_cast_rays_device": (ctypes.c_int, [vp, P(MrtRayBatch), ctypes.c_int32, vp, vp, vp, vp]),
+        "mrt_path_key": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32]),
+        "mrt_shade_rays_device": (ctypes.c_int, [vp, P(MrtShadeBatch), vp, ctypes.c_int64, P(ctypes.c_uint64), vp]),
+        "mrt_camera_rays_device": (ctypes.c_int64, [vp, P(MrtView), ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("MOBILERT_LIB") and not hasattr(lib, name):

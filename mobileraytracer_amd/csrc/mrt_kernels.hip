@@ -1360,7 +1360,12 @@ __device__ __forceinline__ uint32_t querySource(const QueryTables& tb, int32_t k
     return encodePrim(static_cast<uint32_t>(k), static_cast<uint32_t>(b));
 }
 
-__global__ __launch_bounds__(256) void k_query_load(Level lv, QueryRays q, QueryTables tb, int n, int any, int* counters) {
+// kKeyed (mrt_shade_rays_device): the rays become level-1 records of a frame's kind, rO.w the path key
+// every sampler draw below derives from (keys[g], or without keys pathKey(g, 0)); closest hit only.
+// An instantiation of its own: the hit queries' keeps its registers.
+template <bool kKeyed>
+__global__ __launch_bounds__(256) void k_query_load(Level lv, QueryRays q, QueryTables tb, int n, int any, int* counters,
+                                                    const uint32_t* keys) {
     const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
     if (i == 0) denseCounts(counters, 1, any != 0, n, any ? lv.shadowSegCap : lv.segCap);
     if (i >= n) return;
@@ -1371,6 +1376,13 @@ __global__ __launch_bounds__(256) void k_query_load(Level lv, QueryRays q, Query
     const float dx = d[0], dy = d[1], dz = d[2];
     uint32_t code = kNoPrim;
     if (q.src != nullptr) code = querySource(tb, q.src[2 * g], q.src[2 * g + 1]);
+    if constexpr (kKeyed) {
+        const uint32_t key = keys != nullptr ? keys[g] : pathKey(static_cast<uint32_t>(g), 0u);
+        lv.rO[i] = make_float4(ox, oy, oz, bitsf(key));
+        lv.rD[i] = make_float4(dx, dy, dz, bitsf(code));
+        lv.tree[i] = 1u;
+        return;
+    }
     if (any) {
         lv.sO[i] = make_float4(ox, oy, oz, bitsf(code));
         lv.sD[i] = make_float4(dx, dy, dz, q.dist[g]);
@@ -1405,8 +1417,111 @@ __global__ __launch_bounds__(256) void k_query_store(Level lv, QueryTables tb, i
 
 void launchQueryLoad(const Level& lv, const QueryRays& q, const QueryTables& tb, int n, bool any, int* counters,
                      hipStream_t st) {
-    hipLaunchKernelGGL(k_query_load, dim3(std::max(1, (n + 255) / 256)), dim3(256), 0, st, lv, q, tb, n, any ? 1 : 0,
-                       counters);
+    hipLaunchKernelGGL(k_query_load<false>, dim3(std::max(1, (n + 255) / 256)), dim3(256), 0, st, lv, q, tb, n,
+                       any ? 1 : 0, counters, static_cast<const uint32_t*>(nullptr));
+}
+
+void launchShadeLoad(const Level& lv, const QueryRays& q, const QueryTables& tb, int n, const uint32_t* keys,
+                     int* counters, hipStream_t st) {
+    hipLaunchKernelGGL(k_query_load<true>, dim3(std::max(1, (n + 255) / 256)), dim3(256), 0, st, lv, q, tb, n, 0,
+                       counters, keys);
+}
+
+// ---------------------------------------------------------------------------------------
+// Shaded ray queries (mrt_shade_rays_device): a chunk's radiance out to the caller's array, one thread
+// per ray i of the chunk, ray base + i of the batch at rgb + (base + i) * stride (64-bit: 2^31 - 1
+// rays of any stride).  Bandwidth kernels as the two above: adjacent lanes write adjacent 12-byte (or
+// stride-sized) records with three dword vector stores.
+//
+// k_resolve_store: level 1's resolve folded into the store, as k_resolve_accumulate folds it into the
+// accumulation - the same resolveValue on the same records, so the value incrementalAvg would have
+// been handed, and level 1's radiance records are never written.  tl: the table of levels (kTex 2).
+template <int kShader, int kTex>
+__global__ __launch_bounds__(256) void k_resolve_store(DScene s, Level lv, Level nx, ShadeArgs sa, int deadChildren,
+                                                       int n, long long base, float* rgb, long long stride,
+                                                       const TexLevel* tl) {
+    const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const float4 r = resolveValue<kShader, kTex, false>(s, lv, nx, i, 1, sa, deadChildren, lv.vtx[i], tl);
+    float* o = rgb + (base + i) * stride;
+    o[0] = r.x;
+    o[1] = r.y;
+    o[2] = r.z;
+}
+
+// ... from level 1's radiance records (the single-level shaders, whose shading writes them; tuning
+// key 34 = 0, after k_resolve)
+__global__ __launch_bounds__(256) void k_radiance_store(const float4* res, int n, long long base, float* rgb,
+                                                        long long stride) {
+    const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const float4 r = res[i];
+    float* o = rgb + (base + i) * stride;
+    o[0] = r.x;
+    o[1] = r.y;
+    o[2] = r.z;
+}
+
+bool launchResolveStore(int shader, const DScene& s, const Level& lv, const Level& nx, const ShadeArgs& sa,
+                        bool deadChildren, int n, long long base, float* rgb, long long stride, hipStream_t st,
+                        const TexLevel* texLevels) {
+    const int dead = deadChildren ? 1 : 0;
+    const dim3 blocks(std::max(1, (n + 255) / 256));
+    const bool multi = s.textured > 1 && texLevels != nullptr;  // several textured materials
+    const TexLevel* tl = multi ? texLevels : nullptr;
+#define MRT_LAUNCH_RS(SH, TEX) \
+    hipLaunchKernelGGL((k_resolve_store<SH, TEX>), blocks, dim3(256), 0, st, s, lv, nx, sa, dead, n, base, rgb, stride, tl)
+    if (shader == kShaderPathTracer) {
+        if (multi) MRT_LAUNCH_RS(kShaderPathTracer, 2);
+        else if (s.textured != 0) MRT_LAUNCH_RS(kShaderPathTracer, 1);
+        else MRT_LAUNCH_RS(kShaderPathTracer, 0);
+    } else if (shader == kShaderWhitted) {
+        if (multi) MRT_LAUNCH_RS(kShaderWhitted, 2);
+        else if (s.textured != 0) MRT_LAUNCH_RS(kShaderWhitted, 1);
+        else MRT_LAUNCH_RS(kShaderWhitted, 0);
+    } else {
+        return false;  // single-level shaders: nothing to resolve
+    }
+#undef MRT_LAUNCH_RS
+    return true;
+}
+
+void launchRadianceStore(const float4* res, int n, long long base, float* rgb, long long stride, hipStream_t st) {
+    hipLaunchKernelGGL(k_radiance_store, dim3(std::max(1, (n + 255) / 256)), dim3(256), 0, st, res, n, base, rgb, stride);
+}
+
+// The renderer's camera rays out as a batch (mrt_camera_rays_device): path p's ray as k_raygen's
+// record holds it (the same cameraRay, the view as a.cam), packed xyz, with its path key and its
+// pixel y * width + x.  Null outputs are not written.
+__global__ __launch_bounds__(256) void k_camera_rays(RaygenArgs a, float* orig, float* dir, uint32_t* key,
+                                                     int32_t* pixel) {
+    const uint32_t up = blockIdx.x * blockDim.x + threadIdx.x;  // (nPaths may be 2^31 - 1: compared unsigned)
+    if (up >= static_cast<uint32_t>(a.nPaths)) return;
+    const int p = static_cast<int>(up);
+    float4 o4, d4;
+    cameraRay<false>(a, p, &o4, &d4);
+    const size_t at = static_cast<size_t>(p);
+    if (orig != nullptr) {
+        orig[3 * at] = o4.x;
+        orig[3 * at + 1] = o4.y;
+        orig[3 * at + 2] = o4.z;
+    }
+    if (dir != nullptr) {
+        dir[3 * at] = d4.x;
+        dir[3 * at + 1] = d4.y;
+        dir[3 * at + 2] = d4.z;
+    }
+    if (key != nullptr) key[at] = fbits(o4.w);
+    if (pixel != nullptr) {
+        int x, y;
+        slotToXY(a.map, a.slotBase + p / a.spp, &x, &y);
+        pixel[at] = y * a.width + x;
+    }
+}
+
+void launchCameraRays(const RaygenArgs& a, float* orig, float* dir, uint32_t* key, int32_t* pixel, hipStream_t st) {
+    hipLaunchKernelGGL(k_camera_rays, dim3(static_cast<uint32_t>((static_cast<int64_t>(std::max(1, a.nPaths)) + 255) / 256)), dim3(256), 0, st, a, orig, dir, key,
+                       pixel);
 }
 
 void launchQueryStore(const Level& lv, const QueryTables& tb, int n, bool any, long long base, int32_t* kind,

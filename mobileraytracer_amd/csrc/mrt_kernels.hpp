@@ -304,6 +304,22 @@ void launchQueryLoad(const Level& lv, const QueryRays& q, const QueryTables& tb,
 // written); any: kind = occluded, nothing else
 void launchQueryStore(const Level& lv, const QueryTables& tb, int n, bool any, long long base, int32_t* kind,
                       int32_t* index, float* t, hipStream_t st);
+// Shaded ray queries (mrt_shade_rays_device).  k_query_load's keyed form: n rays of q into lv's queue
+// as level-1 records of a frame's kind - rO.w the path key (keys[base + i]; null: pathKey(base + i, 0)),
+// rD.w the mapped source, tree = 1 - with the dense segment counts.
+void launchShadeLoad(const Level& lv, const QueryRays& q, const QueryTables& tb, int n, const uint32_t* keys,
+                     int* counters, hipStream_t st);
+// k_resolve_store: level 1's resolve and the store of its n paths' radiance in one launch, path i to
+// rgb + (base + i) * stride (floats) - launchResolveAccumulate's value without the fold into pixels
+// (Whitted / PathTracer; false: not launched)
+bool launchResolveStore(int shader, const DScene& s, const Level& lv, const Level& nx, const ShadeArgs& sa,
+                        bool deadChildren, int n, long long base, float* rgb, long long stride, hipStream_t st,
+                        const TexLevel* texLevels = nullptr);
+// k_radiance_store: the same store from level 1's radiance records
+void launchRadianceStore(const float4* res, int n, long long base, float* rgb, long long stride, hipStream_t st);
+// k_camera_rays: path p's camera ray (cameraRay with a.cam, as k_raygen's record) packed xyz to
+// orig / dir + 3 p, its path key and pixel y * width + x; null outputs are not written
+void launchCameraRays(const RaygenArgs& a, float* orig, float* dir, uint32_t* key, int32_t* pixel, hipStream_t st);
 int traceResidentThreadsPerCU();  // max over the trace walks of resident threads per CU
 // out[2 slot], out[2 slot + 1] = real-time counter (100 MHz) before / after a spin of `ticks`
 void launchSpin(unsigned long long* out, int slot, unsigned long long ticks, hipStream_t st);

@@ -416,6 +416,18 @@ struct mrt_renderer {
     mrt::QueryTables queryTables{};
     bool queryReady = false;
     int64_t planSlots = 0;                   // the (virtual) slot count the queue plan was made for
+    int planSpp = 0;                         // ... and its level-1 paths per slot (passSpp)
+    // A shade batch (mrt_shade_rays_device): while it runs, the passes run over its n rays - one slot
+    // and one level-1 path each, loaded from the caller's arrays instead of generated - and end with
+    // the radiance stored at rgb instead of accumulated into pixels; null otherwise.
+    struct ShadeBatch {
+        mrt::QueryRays rays;
+        const uint32_t* keys;
+        float* rgb;
+        long long rgbStride;
+        int64_t n;
+    };
+    const ShadeBatch* shade = nullptr;
     hipStream_t stream = nullptr;
     int overlap = 1;                     // tuning key 3: shadow rays on their own stream
     int skipLast = 1;                    // tuning key 7: no closest-hit walk for the depth-capped last level
@@ -905,14 +917,19 @@ void createShadowStream(mrt_renderer* r) {
 // device memory free once the current queues are released.  Frees nothing: a plan that fails
 // leaves the renderer with the queues it had.
 // The slots a pass runs over: the shard's, or a batch's virtual slots (views x the shard's).
-int64_t passSlots(const mrt_renderer* r) { return static_cast<int64_t>(r->nSlots) * std::max(1, r->views); }
+// (A shade batch: its rays, one level-1 path per slot whatever samplesPixel is.)
+int64_t passSlots(const mrt_renderer* r) {
+    return r->shade != nullptr ? r->shade->n : static_cast<int64_t>(r->nSlots) * std::max(1, r->views);
+}
+// The level-1 paths per slot the queues are planned for
+int passSpp(const mrt_renderer* r) { return r->shade != nullptr ? 1 : std::max(1, r->cfg.samplesPixel); }
 
 mrt_queue_plan_request planRequest(mrt_renderer* r) {
     using namespace mrt;
     mrt_queue_plan_request q{};
     q.levels = r->nLevels;
     q.branching = r->shader == kShaderWhitted ? 2 : r->shader == kShaderPathTracer ? 3 : 1;
-    q.samplesPixel = std::max(1, r->cfg.samplesPixel);
+    q.samplesPixel = passSpp(r);
     q.samplesLight = std::max(1, r->cfg.samplesLight);
     q.textured = r->ds.textured != 0 ? 1 : 0;
     q.segments = kQueueSegs;
@@ -956,6 +973,7 @@ void adoptPlan(mrt_renderer* r, mrt_queue_plan_request q) {
     r->plan = plan;
     r->planBudget = q.byteBudget;
     r->planSlots = q.pixelSlots;
+    r->planSpp = q.samplesPixel;
     r->planStale = false;
     allocQueues(r);
 }
@@ -1007,8 +1025,13 @@ hipEvent_t poolEvent(mrt_renderer::Pipe& p) {
 }
 
 // One pass over this shard's pixel slots: samples [sampleBase, sampleBase + spp).
+// A shade batch (r->shade, spp 1): the pass runs over the batch's rays instead.  Level 1 is loaded
+// from the caller's arrays - so it is never fused and never generated in the walk: the packet walk
+// reads the stored records and k_shade shades them, the path of tuning key 33 = 0 - and its resolve
+// ends in the caller's radiance array instead of the pixels.  Everything below level 1 is the frame's.
 void renderPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t st, int sampleBase, int spp) {
     using namespace mrt;
+    const mrt_renderer::ShadeBatch* batch = r->shade;
     const int shader = r->shader;
     const bool timing = (r->profileFlags & 1) != 0;
     const bool counting = (r->profileFlags & 2) != 0;
@@ -1083,19 +1106,25 @@ void renderPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t
         // the same, at N = 1 (15.8) separate launches are faster, 13.94 vs 14.09 ms
         // (profiles/r06_fused_level1_ab.txt).  (With per-launch events too: the serialised roofline
         // frames time the kernel the timed frames run.)
-        r->ds.fuseShade = r->fuseL1Mode >= 0 ? r->fuseL1Mode : (pathsPerLane < 12.0 ? 1 : 0);
-        const bool fuseL1 = nLevels >= 1 && !(skipLast && nLevels == 1) && !(skipLastShade && nLevels == 1) &&
-                            canFuseLevel1(shader, r->ds, sa);
+        r->ds.fuseShade = batch != nullptr ? 0 : r->fuseL1Mode >= 0 ? r->fuseL1Mode : (pathsPerLane < 12.0 ? 1 : 0);
+        const bool fuseL1 = batch == nullptr && nLevels >= 1 && !(skipLast && nLevels == 1) &&
+                            !(skipLastShade && nLevels == 1) && canFuseLevel1(shader, r->ds, sa);
         r->fusedL1 = fuseL1;
         // Unfused, the packet walk generates the camera rays and stores the records k_shade reads
         // (tuning key 33): no k_raygen launch, no ray reads in the walk
-        const bool genL1 = !fuseL1 && r->genL1 != 0 && nLevels >= 1 && !(skipLast && nLevels == 1) &&
-                           packetLevel1(r->ds);
+        const bool genL1 = batch == nullptr && !fuseL1 && r->genL1 != 0 && nLevels >= 1 &&
+                           !(skipLast && nLevels == 1) && packetLevel1(r->ds);
         // ... and with key 33 = 2 k_shade regenerates them instead of reading stored records
         const bool regenL1 = genL1 && r->genL1 == 2 && (shader == kShaderWhitted || shader == kShaderPathTracer) &&
                              !(skipLastShade && nLevels == 1);
         ra.storeRays = regenL1 ? 0 : 1;
-        if (!fuseL1 && !genL1) launchRaygen(ra, pp.levels[1], pp.counters, st);
+        if (batch != nullptr) {  // the caller's rays slot0 .. slot0 + nChunk - 1, with their keys and sources
+            QueryRays q = batch->rays;
+            q.base = slot64;
+            launchShadeLoad(pp.levels[1], q, r->queryTables, nChunk, batch->keys, pp.counters, st);
+        } else if (!fuseL1 && !genL1) {
+            launchRaygen(ra, pp.levels[1], pp.counters, st);
+        }
         // the walk launches' thread cap (tuning key 28 narrows it; the spill stacks hold traceThreads)
         const int walkThreads = r->walkGridCap > 0 ? std::min(r->traceThreads, r->walkGridCap * kBlock)
                                                    : r->traceThreads;
@@ -1201,13 +1230,22 @@ void renderPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t
             launchResolve(shader, r->ds, pp.levels[l], pp.levels[l + 1], pp.counters, l, sa, r->workGrid, st,
                           skipLastShade && l == nLevels - 1, pp.texLevels);
         }
-        if (!resolveAcc || !launchResolveAccumulate(shader, r->ds, pp.levels[1], pp.levels[2], sa,
-                                                    skipLastShade && 1 == nLevels - 1, aa, dBitmap, dPacked, st,
-                                                    pp.texLevels)) {
+        // (a shade batch: folded into the store of the chunk's radiance, k_resolve_store)
+        const bool dead1 = skipLastShade && 1 == nLevels - 1;
+        const bool folded =
+            resolveAcc && (batch != nullptr
+                               ? launchResolveStore(shader, r->ds, pp.levels[1], pp.levels[2], sa, dead1, nChunk, slot64,
+                                                    batch->rgb, batch->rgbStride, st, pp.texLevels)
+                               : launchResolveAccumulate(shader, r->ds, pp.levels[1], pp.levels[2], sa, dead1, aa, dBitmap,
+                                                         dPacked, st, pp.texLevels));
+        if (!folded) {
             if (resolveAcc)  // (single-level shaders: nothing to resolve)
-                launchResolve(shader, r->ds, pp.levels[1], pp.levels[2], pp.counters, 1, sa, r->workGrid, st,
-                              skipLastShade && 1 == nLevels - 1, pp.texLevels);
-            launchAccumulate(aa, pp.levels[1].res, dBitmap, dPacked, st);
+                launchResolve(shader, r->ds, pp.levels[1], pp.levels[2], pp.counters, 1, sa, r->workGrid, st, dead1,
+                              pp.texLevels);
+            if (batch != nullptr)
+                launchRadianceStore(pp.levels[1].res, nChunk, slot64, batch->rgb, batch->rgbStride, st);
+            else
+                launchAccumulate(aa, pp.levels[1].res, dBitmap, dPacked, st);
         }
         // the statistics so far into the pinned host block, the counters reset; after the last chunk
         // the statistics too
@@ -1225,7 +1263,8 @@ bool runPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t st
     using namespace mrt;
     // (tuning keys 37-39 changed; or the slot count did, between a frame and a batch of views: the
     // chunk is sized for the range the pass runs over, and a plan learned for the other count is dropped)
-    if (r->planStale || r->planSlots != std::max<int64_t>(1, passSlots(r))) planFirst(r);
+    // (... or a shade batch came or went: its slots are single paths)
+    if (r->planStale || r->planSlots != std::max<int64_t>(1, passSlots(r)) || r->planSpp != passSpp(r)) planFirst(r);
     const auto t0 = std::chrono::steady_clock::now();
     renderPass(r, dBitmap, dPacked, st, sampleBase, spp);
     MRT_HIP(hipStreamSynchronize(st));  // (k_tally wrote the pass's statistics into r->hostStats)
@@ -1821,11 +1860,95 @@ void castRays(mrt_renderer* r, mrt::QueryRays q, int64_t n, bool any, int32_t* d
     MRT_HIP(hipGetLastError());
 }
 
+// ---- shaded ray queries (mrt_shade_rays_device) ------------------------------------------------
+// The argument checks, all before any device work, in checkRayBatch's order: the batch and the
+// output first (those checks do not read the renderer).
+mrt_renderer::ShadeBatch checkShadeBatch(const mrt_renderer* r, const mrt_shade_batch* b, float* dRgb, int64_t rgbStride) {
+    if (r == nullptr) throw std::runtime_error("mrt_shade_rays_device: null renderer");
+    if (b == nullptr) throw std::runtime_error("mrt_shade_rays_device: null ray batch");
+    const mrt_ray_batch& rays = b->rays;
+    if (rays.orig == nullptr || rays.dir == nullptr) throw std::runtime_error("mrt_shade_rays_device: null orig / dir");
+    if (dRgb == nullptr) throw std::runtime_error("mrt_shade_rays_device: null d_rgb");
+    if (rays.n < 1 || rays.n > 0x7fffffffLL) throw std::runtime_error("mrt_shade_rays_device: n must be 1 .. 2^31 - 1");
+    auto stride = [](int64_t s, const char* name) -> long long {
+        if (s == 0) return 3;
+        if (s < 3) throw std::runtime_error(std::string("mrt_shade_rays_device: ") + name + " must be 0 (packed) or >= 3 floats");
+        return s;
+    };
+    mrt_renderer::ShadeBatch sb{};
+    sb.rays.orig = rays.orig;
+    sb.rays.dir = rays.dir;
+    sb.rays.dist = nullptr;
+    sb.rays.src = rays.src;
+    sb.rays.origStride = stride(rays.origStride, "origStride");
+    sb.rays.dirStride = stride(rays.dirStride, "dirStride");
+    sb.keys = b->key;
+    sb.rgb = dRgb;
+    sb.rgbStride = stride(rgbStride, "rgbStride");
+    sb.n = rays.n;
+    if (!r->peers.empty()) throw std::runtime_error("mrt_shade_rays_device: device groups are not supported for shade batches");
+    return sb;
+}
+
+// The batch as one pass of the wavefront over its rays (renderPass with r->shade), on the render
+// stream; an overflowed pass is redone with queues planned from its demand, as a frame's is (the
+// store only overwrites: no backup).  The frame's state - its statistics, ray total and sample
+// count - is left alone; rays[0] / rays[1]: the rays and shadow rays the batch built.
+void shadeRays(mrt_renderer* r, const mrt_renderer::ShadeBatch& sb, uint64_t* rays) {
+    if (rays != nullptr) rays[0] = rays[1] = 0;
+    if (r->stopFlag.load()) return;  // as a frame after stopRender
+    (void)queryTables(r);  // (uploaded on the render stream, before the first load)
+    struct Restore {
+        mrt_renderer* r;
+        ~Restore() { r->shade = nullptr; }
+    } restore{r};
+    r->shade = &sb;
+    r->replansFrame = 0;
+    mrt_frame_stats fs{};
+    for (int retry = 0;; ++retry) {
+        fs = mrt_frame_stats{};
+        if (runPass(r, nullptr, nullptr, r->stream, 0, 1, &fs)) break;
+        planAfterOverflow(r, retry);
+    }
+    if (rays != nullptr) {
+        rays[0] = fs.rays;
+        rays[1] = fs.shadowRays;
+    }
+}
+
+// The renderer's camera rays (or a view's through the renderer's pixel sampler) as one k_camera_rays
+// launch on st: the RaygenArgs of a frame's single chunk over every slot of the shard.
+int64_t cameraRays(mrt_renderer* r, const mrt::GCamera& cam, int sampleBase, int spp, float* dOrig, float* dDir,
+                   uint32_t* dKey, int32_t* dPixel, hipStream_t st) {
+    const int64_t paths = static_cast<int64_t>(r->nSlots) * spp;
+    if (paths > 0x7fffffffLL) throw std::runtime_error("mrt_camera_rays_device: pixelSlots x spp beyond 2^31 - 1");
+    if (paths == 0) return 0;
+    mrt::RaygenArgs ra{};
+    ra.cam = cam;
+    ra.map = r->mapByRank[static_cast<size_t>(r->rankIndex)];
+    ra.tables = r->ds.tables;
+    ra.jitter = r->ds.jitterDraws;
+    ra.width = r->cfg.width;
+    ra.height = r->cfg.height;
+    ra.slotBase = 0;
+    ra.nPaths = static_cast<int>(paths);
+    ra.spp = spp;
+    ra.sppTotal = r->cfg.samplesPixel;
+    setPixelSampler(r, &ra);
+    ra.sampleBase = sampleBase;
+    ra.storeRays = 1;
+    mrt::launchCameraRays(ra, dOrig, dDir, dKey, dPixel, st);
+    MRT_HIP(hipGetLastError());
+    return paths;
+}
+
 }  // namespace
 
 extern "C" {
 
 const char* mrt_last_error(void) { return gLastError.c_str(); }
+
+uint32_t mrt_path_key(uint32_t pixel, uint32_t sample) { return mrt::pathKey(pixel, sample); }
 
 int mrt_create(const mrt_config* cfg, mrt_renderer** out) {
     *out = nullptr;
@@ -1999,6 +2122,43 @@ int mrt_cast_rays_device(mrt_renderer* r, const mrt_ray_batch* rays, int32_t any
             MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
         }
     });
+}
+
+int mrt_shade_rays_device(mrt_renderer* r, const mrt_shade_batch* b, float* dRgb, int64_t rgbStride, uint64_t* raysOut,
+                          void* stream) {
+    return guarded([&] {
+        const mrt_renderer::ShadeBatch sb = checkShadeBatch(r, b, dRgb, rgbStride);
+        MRT_HIP(hipSetDevice(r->device));
+        hipStream_t st = stream != nullptr ? static_cast<hipStream_t>(stream) : r->stream;
+        // on the renderer's stream, after the caller's work; the pass ends with that stream
+        // synchronised (runPass reads its statistics), so the radiance is written at the return and
+        // no second event is needed (mrt_render_frame_device)
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinIn, st));
+            MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
+        }
+        shadeRays(r, sb, raysOut);
+    });
+}
+
+int64_t mrt_camera_rays_device(mrt_renderer* r, const mrt_view* view, int32_t sampleBase, int32_t spp, float* dOrig,
+                               float* dDir, uint32_t* dKey, int32_t* dPixel, void* stream) {
+    int64_t paths = -1;
+    const int rc = guarded([&] {
+        if (r == nullptr) throw std::runtime_error("mrt_camera_rays_device: null renderer");
+        if (dOrig == nullptr && dDir == nullptr && dKey == nullptr && dPixel == nullptr)
+            throw std::runtime_error("mrt_camera_rays_device: no output (d_orig, d_dir, d_key and d_pixel all null)");
+        if (sampleBase < 0) throw std::runtime_error("mrt_camera_rays_device: sampleBase must be >= 0");
+        // (the view too is checked before the renderer is read)
+        const mrt::GCamera cam = view == nullptr ? r->cam
+                                                 : cameraOf("mrt_camera_rays_device: view", view->kind, view->position,
+                                                            view->lookAt, view->up, view->a, view->b);
+        MRT_HIP(hipSetDevice(r->device));
+        hipStream_t st = stream != nullptr ? static_cast<hipStream_t>(stream) : r->stream;
+        paths = cameraRays(r, cam, sampleBase, spp > 0 ? spp : std::max(1, r->cfg.samplesPixel), dOrig, dDir, dKey,
+                           dPixel, st);
+    });
+    return rc == 0 ? paths : -1;
 }
 
 int mrt_unpack_gathered(mrt_renderer* r, const int32_t* dGathered, int32_t* dBitmap, void* stream) {
