@@ -17,6 +17,12 @@
  *                             the caller's rays, resident in device memory (no single reference call)
  *   mrt_shade_rays_device     Shader::rayTrace (the whole ray tree) for a batch of the caller's rays: linear
  *                             float radiance per ray (no single reference call)
+ *   mrt_cast_hits_device      the Intersection of Shader::rayTrace's intersection part for a batch of the
+ *                             caller's rays: point, normal, texture coordinates, material (no single
+ *                             reference call)
+ *   mrt_scene_triangles / _planes / _spheres / _materials / _lights
+ *                             Shader::getTriangles / getPlanes / getSpheres / getMaterials / getLights
+ *                             (Shader.hpp:92-100) in the scene's input order
  *   mrt_stop_render           Renderer::stopRender (Renderer.cpp:93-99); JNI rtStopRender
  *   mrt_get_sample            Renderer::getSample (Renderer.cpp:177-179); JNI rtGetSample
  *   mrt_get_total_casted_rays Renderer::getTotalCastedRays (Renderer.cpp:204-207)
@@ -468,6 +474,62 @@ typedef struct mrt_ray_batch {
  * Each output may be NULL (not wanted); at least one wanted output must be non-NULL. */
 int mrt_cast_rays_device(mrt_renderer *r, const mrt_ray_batch *rays, int32_t any,
                          int32_t *d_kind, int32_t *d_index, float *d_t, void *stream);
+
+/* ---- surface records (on the GPU; beyond the reference's entry points) ----
+ * mrt_cast_hits_device: the closest hit of each ray of a caller-supplied batch as a surface record: the
+ * fields of the reference's Intersection (Intersection.hpp: point_, normal_, length_, texCoords_,
+ * material_) and the hit material's coefficients, bit for bit the values the shading kernels read at
+ * that hit (the store kernel calls their device functions).  Closest hit only.
+ *
+ * Each field of mrt_hit_records is a device array, packed (ray i's record at i * width), or NULL (not
+ * wanted: neither fetched nor written).  outSize is sizeof(mrt_hit_records) as the caller was compiled:
+ * at most that many bytes of *out are read and fields beyond them count as NULL; fields are only ever
+ * appended (as mrt_get_queue_info's).  With nothing beyond kind / index / t wanted the call launches
+ * exactly the kernels of mrt_cast_rays_device; with nothing beyond bary / point wanted, a store kernel
+ * that fetches no shading or material record.
+ * A miss (kind 0): index and material -1, t as the walk leaves it, texCoord -1, -1, every other float
+ * field 0; no scene record is read for it.
+ * A light hit (kind 4): bary the light triangle's u, v, normal 0, 0, 0 (no shader reads it), texCoord
+ * -1, -1, material = materials + the light's index: the light's own material (Light::radiance_,
+ * AreaLight.cpp:32-41), which follows the scene's materials in the renderer's table and is what
+ * mrt_scene_lights returns for that light; its Kd is never overwritten by a texel.
+ * Everything else - stream order, no host synchronisation, no allocation after a renderer's first
+ * query, chunks of rayCap[0], sources, state, the refusal of a device group - as
+ * mrt_cast_rays_device, which it shares the chunk loop with.  Argument errors (a NULL handle, batch,
+ * orig, dir or out; outSize too small to hold kind; every field within outSize NULL; n or a stride as
+ * for mrt_cast_rays_device) return -1 before any device work, with a message in mrt_last_error(); the
+ * batch and the outputs are checked before the renderer is read. */
+typedef struct mrt_hit_records {
+    int32_t *kind; int32_t *index; float *t;   /* exactly as mrt_cast_rays_device, any = 0 */
+    float   *bary;      /* 2: the walk's u, v (Triangle.cpp:77,83) for a triangle or a light; 0, 0 otherwise */
+    float   *point;     /* 3: Intersection::point_ = origin + direction * t (Triangle.cpp:99, Plane.cpp:62, Sphere.cpp:71) */
+    float   *normal;    /* 3: Intersection::normal_ (Triangle.cpp:96-97 interpolated and normalised; the plane's
+                              normal; normalize(point - centre) for a sphere); 0, 0, 0 for a light hit */
+    float   *texCoord;  /* 2: Triangle.cpp:98 for a triangle of a textured scene; -1, -1 everywhere else */
+    int32_t *material;  /* the hit's material index in the scene's material order (a light hit: see above) */
+    float   *kd;        /* 3: the Kd the shaders read at this hit: the material's, or the texel where
+                              Shader::rayTrace overwrites it (Shader.cpp:112-120) */
+    float   *ks, *kt, *le;  /* 3 each: the material's Ks, Kt, Le */
+    float   *ior;       /* 1 */
+} mrt_hit_records;
+
+int mrt_cast_hits_device(mrt_renderer *r, const mrt_ray_batch *rays, const mrt_hit_records *out, size_t outSize,
+                         void *stream);
+
+/* Host only (no GPU): the scene cfg names as the renderer holds it, every array in the scene's input
+ * order - the order `index` and `material` of the ray queries refer to - and every float the exact
+ * value the kernels read.  Each returns the count (T, P, S, M, L) or -1; NULL outputs are skipped.
+ * triangles: geom T x 9 (A, AB, AC), normals T x 9 (nA, nB, nC as Triangle's constructor normalises
+ * them, Triangle.cpp:14-26), texCoords T x 6 (tA, tB, tC; -1 where the triangle has none), material T.
+ * planes: normalPoint P x 6 (normal, point).  spheres: centreSqRadius S x 4.
+ * materials: coeffs M x 13 (Le, Kd, Ks, Kt, ior), texture M (the material's texture id, -1: none).
+ * lights: kind L (0 point, 1 area), geom L x 9 (an area light's A, AB, AC; a point light's position, then
+ * zeros), coeffs L x 13 (the light's own material; a light hit's `material` is M + its index here). */
+int64_t mrt_scene_triangles(const mrt_config *cfg, float *geom, float *normals, float *texCoords, int32_t *material);
+int64_t mrt_scene_planes(const mrt_config *cfg, float *normalPoint, int32_t *material);
+int64_t mrt_scene_spheres(const mrt_config *cfg, float *centreSqRadius, int32_t *material);
+int64_t mrt_scene_materials(const mrt_config *cfg, float *coeffs, int32_t *texture);
+int64_t mrt_scene_lights(const mrt_config *cfg, int32_t *kind, float *geom, float *coeffs);
 
 /* ---- shaded ray queries (on the GPU; beyond the reference's entry points) ----
  * mrt_shade_rays_device: the radiance that arrives along each ray of a caller-supplied batch, as

@@ -345,6 +345,77 @@ class Renderer:
             if via is not current:
                 current.wait_stream(via)
 
+    # -- surface records -----------------------------------------------------------------
+    HIT_FIELDS = tuple(name for name, _, _ in _native.HIT_FIELDS)
+
+    def cast_hits_device(self, d_orig: int, d_dir: int, n: int, *, d_src: int = 0, orig_stride: int = 3,
+                         dir_stride: int = 3, stream: int = 0, out_size: Optional[int] = None, **outputs: int) -> None:
+        """mrt_cast_hits_device: the closest hit of ``n`` rays resident in device memory as surface
+        records.  ``outputs``: ``d_kind``, ``d_index``, ``d_t``, ``d_bary``, ``d_point``, ``d_normal``,
+        ``d_texCoord``, ``d_material``, ``d_kd``, ``d_ks``, ``d_kt``, ``d_le``, ``d_ior`` - device
+        pointers as ints to packed arrays (mrt_hit_records), 0 or absent: not wanted.  ``out_size``:
+        the bytes of the structure the library may read (None: all of it).  Rays, ``d_src``, strides
+        and ``stream`` as for cast_rays_device."""
+        rec = _native.MrtHitRecords()
+        for key, value in outputs.items():
+            if not key.startswith("d_") or key[2:] not in self.HIT_FIELDS:
+                raise TypeError("cast_hits_device: unknown output %r" % key)
+            setattr(rec, key[2:], value or None)
+        batch = _native.MrtRayBatch(d_orig or None, d_dir or None, None, d_src or None, int(orig_stride),
+                                    int(dir_stride), int(n))
+        size = ctypes.sizeof(rec) if out_size is None else int(out_size)
+        _native.check(self._lib.mrt_cast_hits_device(self._h, ctypes.byref(batch), ctypes.byref(rec), size,
+                                                     ctypes.c_void_p(stream or None)))
+
+    def cast_hits(self, orig, dirs, src=None, fields=None):
+        """cast_hits_device for torch tensors on the renderer's device, with cast_rays' handling of
+        ``orig`` / ``dirs`` / ``src`` and its stream joining.  Returns a dict of tensors, one per name
+        in ``fields`` (None: all of ``Renderer.HIT_FIELDS``): int32 ``kind`` / ``index`` / ``material``
+        of shape (n,), float32 ``t`` / ``ior`` (n,), ``bary`` / ``texCoord`` (n, 2) and ``point`` /
+        ``normal`` / ``kd`` / ``ks`` / ``kt`` / ``le`` (n, 3), allocated and ordered on torch's current
+        stream.  An empty batch returns empty tensors."""
+        import torch
+
+        device, n, orig, orig_stride, dirs, dir_stride = self._ray_tensors(orig, dirs)
+        fields = self.HIT_FIELDS if fields is None else tuple(fields)
+        if not fields or any(f not in self.HIT_FIELDS for f in fields):
+            raise ValueError("fields: at least one of %s" % (self.HIT_FIELDS,))
+        if src is not None:
+            if src.device != device or src.shape != (n, 2):
+                raise ValueError("src: a tensor of shape (%d, 2) on %s" % (n, device))
+            src = src.to(torch.int32).contiguous()
+        out = {}
+        for name, dtype, width in _native.HIT_FIELDS:
+            if name in fields:
+                out[name] = torch.empty(n if width == 1 else (n, width), dtype=getattr(torch, dtype), device=device)
+        if n == 0:
+            return out
+        with self._query_stream_of(device) as stream:
+            self.cast_hits_device(orig.data_ptr(), dirs.data_ptr(), n, d_src=src.data_ptr() if src is not None else 0,
+                                  orig_stride=orig_stride, dir_stride=dir_stride, stream=stream,
+                                  **{"d_" + name: x.data_ptr() for name, x in out.items()})
+        return out
+
+    def first_hit_planes(self, camera=None, sample: int = 0, fields=None):
+        """The first hit of every pixel's camera ray (sample ``sample``) as planes: camera_rays(camera,
+        sample_base=sample, spp=1), then cast_hits, scattered by ``pixels`` into (height, width) or
+        (height, width, c) tensors - the guide planes (albedo ``kd``, ``normal``, depth ``t``) a
+        denoiser wants for a frame.  Pixels this shard does not own keep ``kind`` 0, ``index`` and
+        ``material`` -1, ``texCoord`` -1 and 0 elsewhere."""
+        import torch
+
+        orig, dirs, _, pixels = self.camera_rays(camera, sample_base=sample, spp=1)
+        recs = self.cast_hits(orig, dirs, fields=fields)
+        h, w = self.config.height, self.config.width
+        at = pixels.to(torch.int64)
+        planes = {}
+        for name, x in recs.items():
+            fill = -1 if name in ("index", "material", "texCoord") else 0
+            plane = torch.full((h * w,) + tuple(x.shape[1:]), fill, dtype=x.dtype, device=x.device)
+            plane[at] = x
+            planes[name] = plane.reshape((h, w) + tuple(x.shape[1:]))
+        return planes
+
     # -- shaded ray queries --------------------------------------------------------------
     def shade_rays_device(self, d_orig: int, d_dir: int, n: int, *, d_key: int = 0, d_src: int = 0,
                           orig_stride: int = 3, dir_stride: int = 3, d_rgb: int, rgb_stride: int = 3,
@@ -493,6 +564,52 @@ def triangle_bvh(config: Config):
     if n2 != n:
         raise RuntimeError(lib.mrt_last_error().decode())
     return boxes, off, cnt, order[:int(cnt[0])] if n == 1 else order
+
+
+def _scene_arrays(name, config, shapes):
+    """A host-only scene accessor (mrt_scene_*): the count first, then the arrays of the given
+    (dtype, per-item shape) filled in the scene's input order."""
+    lib = _native.lib()
+    fn = getattr(lib, name)
+    c = config.to_c()
+    n = fn(ctypes.byref(c), *([None] * len(shapes)))
+    if n < 0:
+        raise RuntimeError(lib.mrt_last_error().decode())
+    arrays = [np.zeros((n,) + shape, dtype) for dtype, shape in shapes]
+    if fn(ctypes.byref(c), *[_ptr(a) for a in arrays]) != n:
+        raise RuntimeError(lib.mrt_last_error().decode())
+    return arrays
+
+
+def scene_triangles(config: Config):
+    """Host only (mrt_scene_triangles): the configured scene's triangles in input order - the order
+    ``index`` of the ray queries refers to - as the renderer holds them: geom (T, 3, 3) float32 (A, AB,
+    AC), normals (T, 3, 3) (nA, nB, nC), texCoords (T, 3, 2) (-1 where none), material (T,) int32."""
+    return tuple(_scene_arrays("mrt_scene_triangles", config, [(np.float32, (3, 3)), (np.float32, (3, 3)),
+                                                               (np.float32, (3, 2)), (np.int32, ())]))
+
+
+def scene_planes(config: Config):
+    """Host only (mrt_scene_planes): normalPoint (P, 2, 3) float32 (normal, point), material (P,) int32."""
+    return tuple(_scene_arrays("mrt_scene_planes", config, [(np.float32, (2, 3)), (np.int32, ())]))
+
+
+def scene_spheres(config: Config):
+    """Host only (mrt_scene_spheres): centreSqRadius (S, 4) float32, material (S,) int32."""
+    return tuple(_scene_arrays("mrt_scene_spheres", config, [(np.float32, (4,)), (np.int32, ())]))
+
+
+def scene_materials(config: Config):
+    """Host only (mrt_scene_materials): coeffs (M, 13) float32 (Le, Kd, Ks, Kt, ior) in the order
+    ``material`` of cast_hits refers to, texture (M,) int32 (the texture id, -1: none)."""
+    return tuple(_scene_arrays("mrt_scene_materials", config, [(np.float32, (13,)), (np.int32, ())]))
+
+
+def scene_lights(config: Config):
+    """Host only (mrt_scene_lights): kind (L,) int32 (0 point, 1 area), geom (L, 3, 3) float32 (A, AB, AC
+    of an area light; a point light's position, then zeros), coeffs (L, 13) float32: the light's own
+    material, which a light hit of cast_hits names as ``material`` = M + the light's index."""
+    return tuple(_scene_arrays("mrt_scene_lights", config, [(np.int32, ()), (np.float32, (3, 3)), (np.float32, (13,))]))
 
 
 def plan_queues(levels: int, branching: int, pixel_slots: int, samples_pixel: int = 1, samples_light: int = 1,

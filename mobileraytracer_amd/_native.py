@@ -28,6 +28,8 @@ EXPORTED_SYMBOLS = (
     "mrt_get_queue_info", "mrt_plan_queues", "mrt_render_views", "mrt_render_views_device",
     "mrt_kat_accumulate", "mrt_cast_rays_device", "mrt_walk_stack", "mrt_plan_spill",
     "mrt_path_key", "mrt_shade_rays_device", "mrt_camera_rays_device",
+    "mrt_cast_hits_device", "mrt_scene_triangles", "mrt_scene_planes", "mrt_scene_spheres", "mrt_scene_materials",
+    "mrt_scene_lights",
     "RayTrace", "stopRender",
 )
 
@@ -63,6 +65,16 @@ class MrtView(ctypes.Structure):  # mrt_view: the arguments of mrt_set_camera
 class MrtRayBatch(ctypes.Structure):  # mrt_ray_batch: a device-resident batch of rays (mrt_cast_rays_device)
     _fields_ = [("orig", ctypes.c_void_p), ("dir", ctypes.c_void_p), ("dist", ctypes.c_void_p), ("src", ctypes.c_void_p),
                 ("origStride", ctypes.c_int64), ("dirStride", ctypes.c_int64), ("n", ctypes.c_int64)]
+
+
+# mrt_hit_records: the fields in the header's order, (name, dtype, floats or ints per ray)
+HIT_FIELDS = (("kind", "int32", 1), ("index", "int32", 1), ("t", "float32", 1), ("bary", "float32", 2),
+              ("point", "float32", 3), ("normal", "float32", 3), ("texCoord", "float32", 2), ("material", "int32", 1),
+              ("kd", "float32", 3), ("ks", "float32", 3), ("kt", "float32", 3), ("le", "float32", 3), ("ior", "float32", 1))
+
+
+class MrtHitRecords(ctypes.Structure):  # mrt_hit_records: device arrays of a surface-record query, NULL = not wanted
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in HIT_FIELDS]
 
 
 class MrtShadeBatch(ctypes.Structure):  # mrt_shade_batch: rays and their path keys (mrt_shade_rays_device)
@@ -207,6 +219,12 @@ def load_library(path=LIB_PATH):
         "mrt_kat_accumulate": (ctypes.c_int, [vp] + [ctypes.c_int32] * 6 + [vp, P(ctypes.c_int32)]),
         "mrt_trace_rays": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]),
         "mrt_cast_rays_device": (ctypes.c_int, [vp, P(MrtRayBatch), ctypes.c_int32, vp, vp, vp, vp]),
+        "mrt_cast_hits_device": (ctypes.c_int, [vp, P(MrtRayBatch), P(MrtHitRecords), ctypes.c_size_t, vp]),
+        "mrt_scene_triangles": (ctypes.c_int64, [vp, vp, vp, vp, vp]),
+        "mrt_scene_planes": (ctypes.c_int64, [vp, vp, vp]),
+        "mrt_scene_spheres": (ctypes.c_int64, [vp, vp, vp]),
+        "mrt_scene_materials": (ctypes.c_int64, [vp, vp, vp]),
+        "mrt_scene_lights": (ctypes.c_int64, [vp, vp, vp, vp]),
         "mrt_path_key": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32]),
         "mrt_shade_rays_device": (ctypes.c_int, [vp, P(MrtShadeBatch), vp, ctypes.c_int64, P(ctypes.c_uint64), vp]),
         "mrt_camera_rays_device": (ctypes.c_int64, [vp, P(MrtView), ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp]),

@@ -1415,6 +1415,118 @@ __global__ __launch_bounds__(256) void k_query_store(Level lv, QueryTables tb, i
     if (t != nullptr) t[g] = h.x;
 }
 
+// Surface records (mrt_cast_hits_device): k_query_store's outputs, then Intersection's fields and the
+// hit material's coefficients, through the device functions the shading kernels call (hitGeometry,
+// hitMaterial, textureWrite), so the bits are the shading's own.  A bandwidth kernel as its neighbours:
+// every gather is issued before the first store, adjacent lanes write adjacent 4-, 8- or 12-byte
+// records with dword stores, and a null output costs neither its gather nor its store.
+// kFull = false (geometry only: kind, index, t, bary, point) fetches no shading or material record.
+// A miss writes index and material -1, texCoord -1, -1, t as the walk left it and 0 elsewhere, and
+// reads no scene record; a light hit reads its light record and the light's own material only.
+__device__ __forceinline__ void store2(float* p, long long g, float a, float b) {
+    if (p == nullptr) return;
+    p[2 * g] = a;
+    p[2 * g + 1] = b;
+}
+__device__ __forceinline__ void store3(float* p, long long g, v3 a) {
+    if (p == nullptr) return;
+    p[3 * g] = a.x;
+    p[3 * g + 1] = a.y;
+    p[3 * g + 2] = a.z;
+}
+
+template <bool kFull>
+__global__ __launch_bounds__(256) void k_query_store_hits(DScene s, Level lv, QueryTables tb, int n, long long base,
+                                                          HitRecords out) {
+    const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const long long g = base + i;
+    const float4 h = lv.hit[i];
+    const uint32_t code = fbits(h.w);
+    const uint32_t k = primKind(code);
+    const bool hit = k != kMiss;
+    const bool tri = k == kTriangle;
+    const bool surface = hit && k != kLight;  // a plane, sphere or triangle: what hitGeometry / hitMaterial take
+    int32_t index = -1;
+    if (out.index != nullptr && hit) {
+        const int32_t* order = tri ? tb.triOrder : k == kPlane ? tb.planeOrder : k == kSphere ? tb.sphereOrder : nullptr;
+        const int32_t b = static_cast<int32_t>(primIndex(code));
+        index = order != nullptr ? order[b] : b;
+    }
+    const v3 zero{0.0F, 0.0F, 0.0F};
+    v3 P = zero, N = zero;
+    const bool wantN = kFull && out.normal != nullptr;
+    if ((out.point != nullptr || wantN) && hit) {
+        const v3 o = xyz(lv.rO[i]), d = xyz(lv.rD[i]);
+        if (wantN && surface) {
+            const HitGeom hg = hitGeometry(s, o, d, h);
+            P = hg.P;
+            N = hg.N;
+        } else {
+            P = o + d * h.x;  // hitGeometry's point (Triangle.cpp:99, Plane.cpp:62, Sphere.cpp:71)
+        }
+    }
+    float tx = -1.0F, ty = -1.0F;
+    int32_t mi = -1;
+    v3 Kd = zero, Ks = zero, Kt = zero, Le = zero;
+    float ior = 0.0F;
+    if constexpr (kFull) {
+        if (out.texCoord != nullptr && tri && s.textured != 0) {  // Triangle.cpp:98, in textureWrite's association
+            const uint32_t j = primIndex(code);
+            const float4 a = s.triTex[2 * j], b = s.triTex[2 * j + 1];
+            const float w = 1.0F - h.y - h.z;
+            tx = (a.x * w + a.z * h.y) + b.x * h.z;
+            ty = (a.y * w + a.w * h.y) + b.y * h.z;
+        }
+        const bool wantMat = out.material != nullptr || out.kd != nullptr || out.ks != nullptr || out.kt != nullptr ||
+                             out.le != nullptr || out.ior != nullptr;
+        if (wantMat && hit) {
+            // a light hit carries the light's own material (k_shade_simple)
+            mi = k == kLight ? __float_as_int(s.lights[4 * primIndex(code) + 3].w) : hitMaterial(s, code);
+            const float4* m = s.mats + 4 * mi;
+            if (out.le != nullptr || out.ior != nullptr) {
+                const float4 le4 = m[0];
+                Le = xyz(le4);
+                ior = le4.w;
+            }
+            if (out.kd != nullptr) {
+                Kd = xyz(m[1]);
+                if (s.textured != 0 && k != kLight) {  // Shader.cpp:112-120
+                    const float4 kw = textureWrite(s, h);
+                    if (kw.w >= 0.0F) Kd = xyz(kw);
+                }
+            }
+            if (out.ks != nullptr) Ks = xyz(m[2]);
+            if (out.kt != nullptr) Kt = xyz(m[3]);
+        }
+    }
+    if (out.kind != nullptr) out.kind[g] = static_cast<int32_t>(k);
+    if (out.index != nullptr) out.index[g] = index;
+    if (out.t != nullptr) out.t[g] = h.x;
+    const bool uv = tri || k == kLight;  // the walk's u, v of a triangle test (Triangle.cpp:77,83)
+    store2(out.bary, g, uv ? h.y : 0.0F, uv ? h.z : 0.0F);
+    store3(out.point, g, P);
+    if constexpr (kFull) {
+        store3(out.normal, g, N);
+        store2(out.texCoord, g, tx, ty);
+        if (out.material != nullptr) out.material[g] = mi;
+        store3(out.kd, g, Kd);
+        store3(out.ks, g, Ks);
+        store3(out.kt, g, Kt);
+        store3(out.le, g, Le);
+        if (out.ior != nullptr) out.ior[g] = ior;
+    }
+}
+
+void launchQueryStoreHits(const DScene& s, const Level& lv, const QueryTables& tb, int n, long long base,
+                          const HitRecords& out, hipStream_t st) {
+    const dim3 blocks(std::max(1, (n + 255) / 256));
+    if (out.beyondGeometry())
+        hipLaunchKernelGGL(k_query_store_hits<true>, blocks, dim3(256), 0, st, s, lv, tb, n, base, out);
+    else
+        hipLaunchKernelGGL(k_query_store_hits<false>, blocks, dim3(256), 0, st, s, lv, tb, n, base, out);
+}
+
 void launchQueryLoad(const Level& lv, const QueryRays& q, const QueryTables& tb, int n, bool any, int* counters,
                      hipStream_t st) {
     hipLaunchKernelGGL(k_query_load<false>, dim3(std::max(1, (n + 255) / 256)), dim3(256), 0, st, lv, q, tb, n,

@@ -304,6 +304,34 @@ void launchQueryLoad(const Level& lv, const QueryRays& q, const QueryTables& tb,
 // written); any: kind = occluded, nothing else
 void launchQueryStore(const Level& lv, const QueryTables& tb, int n, bool any, long long base, int32_t* kind,
                       int32_t* index, float* t, hipStream_t st);
+// Surface records (mrt_cast_hits_device): the device arrays of mrt_hit_records, each packed (ray g's
+// record at g * width) or null (not wanted: neither gathered nor stored).
+struct HitRecords {
+    int32_t* kind;
+    int32_t* index;
+    float* t;
+    float* bary;      // 2
+    float* point;     // 3
+    float* normal;    // 3
+    float* texCoord;  // 2
+    int32_t* material;
+    float* kd;        // 3
+    float* ks;        // 3
+    float* kt;        // 3
+    float* le;        // 3
+    float* ior;
+    bool beyondHit() const { return beyondGeometry() || bary != nullptr || point != nullptr; }  // more than k_query_store writes
+    bool beyondGeometry() const {
+        return normal != nullptr || texCoord != nullptr || material != nullptr || kd != nullptr || ks != nullptr ||
+               kt != nullptr || le != nullptr || ior != nullptr;
+    }
+};
+// k_query_store_hits: the closest-hit walk's results of those n rays as surface records at base + i: what
+// k_query_store writes, then the hit's geometry and material through the shading's own device functions
+// (hitGeometry, hitMaterial, textureWrite).  Two instantiations: geometry only (kind, index, t, bary,
+// point: no shading or material record is fetched) where out.beyondGeometry() is false, else the full one.
+void launchQueryStoreHits(const DScene& s, const Level& lv, const QueryTables& tb, int n, long long base,
+                          const HitRecords& out, hipStream_t st);
 // Shaded ray queries (mrt_shade_rays_device).  k_query_load's keyed form: n rays of q into lv's queue
 // as level-1 records of a frame's kind - rO.w the path key (keys[base + i]; null: pathKey(base + i, 0)),
 // rD.w the mapped source, tree = 1 - with the dense segment counts.

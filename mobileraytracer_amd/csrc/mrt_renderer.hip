@@ -1832,7 +1832,9 @@ const mrt::QueryTables& queryTables(mrt_renderer* r) {
 
 // The batch through level 1's queue, a chunk of its capacity at a time, all enqueued on the render
 // stream: counters reset, rays loaded, walked, results stored.  Nothing waits on the host.
-void castRays(mrt_renderer* r, mrt::QueryRays q, int64_t n, bool any, int32_t* dKind, int32_t* dIndex, float* dT) {
+// rec (mrt_cast_hits_device): the chunk's results stored as surface records instead.
+void castRays(mrt_renderer* r, mrt::QueryRays q, int64_t n, bool any, int32_t* dKind, int32_t* dIndex, float* dT,
+              const mrt::HitRecords* rec = nullptr) {
     using namespace mrt;
     hipStream_t st = r->stream;
     const QueryTables& tb = queryTables(r);
@@ -1855,9 +1857,72 @@ void castRays(mrt_renderer* r, mrt::QueryRays q, int64_t n, bool any, int32_t* d
             launchShadow(r->ds, lv, pp.counters, 1, pp.gstackShadow, r->gdepth, pp.stats, false, walkThreads, st);
         else
             launchTrace(r->ds, lv, pp.counters, 1, pp.gstack, r->gdepth, pp.stats, false, walkThreads, st);
-        launchQueryStore(lv, tb, m, any, base, dKind, dIndex, dT, st);
+        if (rec != nullptr)
+            launchQueryStoreHits(r->ds, lv, tb, m, base, *rec, st);
+        else
+            launchQueryStore(lv, tb, m, any, base, dKind, dIndex, dT, st);
     }
     MRT_HIP(hipGetLastError());
+}
+
+// ---- host-only scene accessors: the loaded scene in its input order, the floats the renderer holds ----
+mrt::HScene sceneOf(const mrt_config* cfg) {
+    using namespace mrt;
+    if (cfg == nullptr) throw std::runtime_error("null config");
+    if (cfg->sceneIndex >= 0 && cfg->sceneIndex <= 3) return builtinScene(cfg->sceneIndex);
+    HScene sc;
+    std::string err;
+    if (!loadObjScene(cfg->objFilePath ? cfg->objFilePath : "", cfg->mtlFilePath ? cfg->mtlFilePath : "", &sc, &err))
+        throw std::runtime_error(err);
+    return sc;
+}
+void put3(float* out, mrt::v3 a) {
+    out[0] = a.x;
+    out[1] = a.y;
+    out[2] = a.z;
+}
+void putMaterial(float* out, const mrt::HMaterial& m) {  // Le, Kd, Ks, Kt, ior
+    put3(out, m.Le);
+    put3(out + 3, m.Kd);
+    put3(out + 6, m.Ks);
+    put3(out + 9, m.Kt);
+    out[12] = m.ior;
+}
+
+// ---- surface records (mrt_cast_hits_device) ----------------------------------------------------
+// The argument checks, all before any device work, the batch and the outputs before the renderer is
+// read; fills the batch with its strides resolved and the records: the first outSize bytes of *out,
+// whole fields only, every field beyond them null.
+mrt::QueryRays checkHitBatch(const mrt_renderer* r, const mrt_ray_batch* rays, const mrt_hit_records* out, size_t outSize,
+                             mrt::HitRecords* rec) {
+    if (r == nullptr) throw std::runtime_error("mrt_cast_hits_device: null renderer");
+    if (rays == nullptr) throw std::runtime_error("mrt_cast_hits_device: null ray batch");
+    if (rays->orig == nullptr || rays->dir == nullptr) throw std::runtime_error("mrt_cast_hits_device: null orig / dir");
+    if (out == nullptr) throw std::runtime_error("mrt_cast_hits_device: null hit records");
+    if (outSize < offsetof(mrt_hit_records, kind) + sizeof(out->kind))
+        throw std::runtime_error("mrt_cast_hits_device: outSize too small to hold kind");
+    static_assert(sizeof(mrt_hit_records) == 13 * sizeof(void*), "mrt_hit_records: pointers only (fields are appended)");
+    mrt_hit_records o{};
+    std::memcpy(&o, out, std::min(outSize, sizeof(o)) / sizeof(void*) * sizeof(void*));
+    *rec = mrt::HitRecords{o.kind, o.index, o.t,  o.bary, o.point, o.normal, o.texCoord,
+                           o.material, o.kd, o.ks, o.kt,   o.le,    o.ior};
+    if (rec->kind == nullptr && rec->index == nullptr && rec->t == nullptr && !rec->beyondHit())
+        throw std::runtime_error("mrt_cast_hits_device: no output (every field within outSize is null)");
+    if (rays->n < 1 || rays->n > 0x7fffffffLL) throw std::runtime_error("mrt_cast_hits_device: n must be 1 .. 2^31 - 1");
+    auto stride = [](int64_t s, const char* name) -> long long {
+        if (s == 0) return 3;
+        if (s < 3) throw std::runtime_error(std::string("mrt_cast_hits_device: ") + name + " must be 0 (packed) or >= 3 floats");
+        return s;
+    };
+    mrt::QueryRays q{};
+    q.orig = rays->orig;
+    q.dir = rays->dir;
+    q.dist = nullptr;
+    q.src = rays->src;
+    q.origStride = stride(rays->origStride, "origStride");
+    q.dirStride = stride(rays->dirStride, "dirStride");
+    if (!r->peers.empty()) throw std::runtime_error("mrt_cast_hits_device: device groups are not supported for ray queries");
+    return q;
 }
 
 // ---- shaded ray queries (mrt_shade_rays_device) ------------------------------------------------
@@ -2124,6 +2189,27 @@ int mrt_cast_rays_device(mrt_renderer* r, const mrt_ray_batch* rays, int32_t any
     });
 }
 
+int mrt_cast_hits_device(mrt_renderer* r, const mrt_ray_batch* rays, const mrt_hit_records* out, size_t outSize,
+                         void* stream) {
+    return guarded([&] {
+        mrt::HitRecords rec{};
+        const mrt::QueryRays q = checkHitBatch(r, rays, out, outSize, &rec);
+        MRT_HIP(hipSetDevice(r->device));
+        hipStream_t st = stream != nullptr ? static_cast<hipStream_t>(stream) : r->stream;
+        // joined to the caller's stream on both sides, as mrt_cast_rays_device
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinIn, st));
+            MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
+        }
+        // nothing beyond kind / index / t wanted: the hit query's own store kernel
+        castRays(r, q, rays->n, false, rec.kind, rec.index, rec.t, rec.beyondHit() ? &rec : nullptr);
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinOut, r->stream));
+            MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
+        }
+    });
+}
+
 int mrt_shade_rays_device(mrt_renderer* r, const mrt_shade_batch* b, float* dRgb, int64_t rgbStride, uint64_t* raysOut,
                           void* stream) {
     return guarded([&] {
@@ -2380,6 +2466,99 @@ int64_t mrt_triangle_bvh(const mrt_config* cfg, float* boxes, int32_t* offsets, 
             counts[i] = b.numPrimitives;
         }
         std::memcpy(order, perm.data(), perm.size() * sizeof(int32_t));
+    });
+    return rc == 0 ? n : -1;
+}
+
+// ---- host-only scene accessors (helpers above: sceneOf, putMaterial) ----
+int64_t mrt_scene_triangles(const mrt_config* cfg, float* geom, float* normals, float* texCoords, int32_t* material) {
+    int64_t n = -1;
+    const int rc = guarded([&] {
+        const mrt::HScene sc = sceneOf(cfg);
+        for (size_t i = 0; i < sc.triangles.size(); ++i) {
+            const mrt::HTriangle& t = sc.triangles[i];
+            if (geom != nullptr) {
+                put3(geom + 9 * i, t.A);
+                put3(geom + 9 * i + 3, t.AB);
+                put3(geom + 9 * i + 6, t.AC);
+            }
+            if (normals != nullptr) {
+                put3(normals + 9 * i, t.nA);
+                put3(normals + 9 * i + 3, t.nB);
+                put3(normals + 9 * i + 6, t.nC);
+            }
+            if (texCoords != nullptr) {
+                const float tc[6] = {t.tA.x, t.tA.y, t.tB.x, t.tB.y, t.tC.x, t.tC.y};
+                std::memcpy(texCoords + 6 * i, tc, sizeof(tc));
+            }
+            if (material != nullptr) material[i] = t.mat;
+        }
+        n = static_cast<int64_t>(sc.triangles.size());
+    });
+    return rc == 0 ? n : -1;
+}
+
+int64_t mrt_scene_planes(const mrt_config* cfg, float* normalPoint, int32_t* material) {
+    int64_t n = -1;
+    const int rc = guarded([&] {
+        const mrt::HScene sc = sceneOf(cfg);
+        for (size_t i = 0; i < sc.planes.size(); ++i) {
+            if (normalPoint != nullptr) {
+                put3(normalPoint + 6 * i, sc.planes[i].normal);
+                put3(normalPoint + 6 * i + 3, sc.planes[i].point);
+            }
+            if (material != nullptr) material[i] = sc.planes[i].mat;
+        }
+        n = static_cast<int64_t>(sc.planes.size());
+    });
+    return rc == 0 ? n : -1;
+}
+
+int64_t mrt_scene_spheres(const mrt_config* cfg, float* centreSqRadius, int32_t* material) {
+    int64_t n = -1;
+    const int rc = guarded([&] {
+        const mrt::HScene sc = sceneOf(cfg);
+        for (size_t i = 0; i < sc.spheres.size(); ++i) {
+            if (centreSqRadius != nullptr) {
+                put3(centreSqRadius + 4 * i, sc.spheres[i].center);
+                centreSqRadius[4 * i + 3] = sc.spheres[i].sqRadius;
+            }
+            if (material != nullptr) material[i] = sc.spheres[i].mat;
+        }
+        n = static_cast<int64_t>(sc.spheres.size());
+    });
+    return rc == 0 ? n : -1;
+}
+
+int64_t mrt_scene_materials(const mrt_config* cfg, float* coeffs, int32_t* texture) {
+    int64_t n = -1;
+    const int rc = guarded([&] {
+        const mrt::HScene sc = sceneOf(cfg);
+        for (size_t i = 0; i < sc.materials.size(); ++i) {
+            if (coeffs != nullptr) putMaterial(coeffs + 13 * i, sc.materials[i]);
+            if (texture != nullptr) texture[i] = sc.materials[i].texId;
+        }
+        n = static_cast<int64_t>(sc.materials.size());
+    });
+    return rc == 0 ? n : -1;
+}
+
+int64_t mrt_scene_lights(const mrt_config* cfg, int32_t* kind, float* geom, float* coeffs) {
+    int64_t n = -1;
+    const int rc = guarded([&] {
+        const mrt::HScene sc = sceneOf(cfg);
+        for (size_t i = 0; i < sc.lights.size(); ++i) {
+            const mrt::HLight& l = sc.lights[i];
+            const bool area = l.kind == mrt::kAreaLight;
+            if (kind != nullptr) kind[i] = l.kind;
+            if (geom != nullptr) {
+                put3(geom + 9 * i, area ? l.tri.A : l.position);
+                put3(geom + 9 * i + 3, area ? l.tri.AB : mrt::v3{0, 0, 0});
+                put3(geom + 9 * i + 6, area ? l.tri.AC : mrt::v3{0, 0, 0});
+            }
+            if (coeffs != nullptr) putMaterial(coeffs + 13 * i, l.radiance);
+        }
+        n = static_cast<int64_t>(sc.lights.size());
     });
     return rc == 0 ? n : -1;
 }
