@@ -20,6 +20,10 @@
  *   mrt_cast_hits_device      the Intersection of Shader::rayTrace's intersection part for a batch of the
  *                             caller's rays: point, normal, texture coordinates, material (no single
  *                             reference call)
+ *   mrt_cast_multi_hits_device
+ *                             the first K hits along each of the caller's rays, in order, and the hit count:
+ *                             every hit Shader::rayTrace's intersection part would accept on an unshortened
+ *                             ray (no single reference call)
  *   mrt_scene_triangles / _planes / _spheres / _materials / _lights
  *                             Shader::getTriangles / getPlanes / getSpheres / getMaterials / getLights
  *                             (Shader.hpp:92-100) in the scene's input order
@@ -461,7 +465,8 @@ int mrt_trace_rays(mrt_renderer *r, const float *orig, const float *dir, const f
 typedef struct mrt_ray_batch {
     const float   *orig;        /* device: ray i's origin xyz at orig + i * origStride */
     const float   *dir;         /* device: ray i's direction xyz at dir + i * dirStride */
-    const float   *dist;        /* device, any-hit only: tmax per ray (n floats); ignored for closest hit */
+    const float   *dist;        /* device, any-hit only: tmax per ray (n floats); ignored for closest hit
+                                   (mrt_cast_multi_hits_device: optional tmax per ray, NULL = RayLengthMax) */
     const int32_t *src;         /* device or NULL: n pairs (kind, input index) of the primitive a ray leaves */
     int64_t origStride;         /* in floats, >= 3; 0 means 3.  6 reads an (n, 6) origin|direction array */
     int64_t dirStride;
@@ -515,6 +520,57 @@ typedef struct mrt_hit_records {
 
 int mrt_cast_hits_device(mrt_renderer *r, const mrt_ray_batch *rays, const mrt_hit_records *out, size_t outSize,
                          void *stream);
+
+/* ---- multi-hit queries (on the GPU; beyond the reference's entry points) ----
+ * mrt_cast_multi_hits_device: the first K hits along each ray of a caller-supplied batch, in order, and
+ * the number of hits: what lies behind the first surface (a lidar's later returns, the walls between two
+ * points, the thickness of glass, picking through a pane, inside / outside parity) in one walk and with
+ * the reference's own t, instead of K re-casts from a moved origin.
+ *
+ * The hit set of ray i, with interval end tmax_i = rays->dist[i] (here dist is optional: NULL means
+ * RayLengthMax for every ray), is every primitive that Shader::rayTrace's intersection part
+ * (Shader.cpp:86-111) would accept if no accepted hit shortened the ray:
+ *   tested:   every plane, sphere and triangle the accelerator tests for this ray, and every area light
+ *             (Shader.cpp:166-171).  BVH (accelerator 3): the reference's visit set, the leaves whose own
+ *             box and every ancestor's box pass AABB::intersect (as with no cull).  Naive (1): every
+ *             primitive.  An accelerator id that builds nothing: the lights only.
+ *   accepted: the primitive's intersect accepts at length tmax_i: neither t < Epsilon (EpsilonLarge for
+ *             a sphere) nor t >= tmax_i.  A src triangle or plane excludes itself, as in
+ *             mrt_cast_rays_device.
+ *   NaN t:    a hit whose t is NaN (non-finite geometry) is left out of the set and out of the count.
+ *             This is the one place where the list departs from the reference's acceptance (which takes
+ *             such a hit, Triangle.cpp:104): an ordered list has no place for NaN.
+ * count[i] is the size of the hit set, not capped by K.
+ * The list is the first min(count, K) members in the walks' total order: by t; on bit-equal t by kind
+ * in the order the reference evaluates them (plane, sphere, triangle, light); within a kind by the index
+ * the closest-hit walk prefers: the lower BVH-order (walk-order) index under BVH, the lower input index
+ * under Naive.  With dist NULL entry 0 is therefore mrt_cast_rays_device's closest hit, bit for bit
+ * (kind, index, t), on every scene whose hits are all ordered (no NaN t).
+ * Entries count .. K - 1 are padding: kind 0, index -1, t = tmax_i, bary 0, 0.
+ * Each field of mrt_multi_hits is a packed device array or NULL (not wanted: not written); outSize is
+ * sizeof(mrt_multi_hits) as the caller was compiled, as for mrt_cast_hits_device: fields beyond it count
+ * as NULL, and fields are only ever appended.
+ * RegularGrid (accelerator 2) is refused: -1 with a message, nothing done.  The grid's visit set depends
+ * on where the closest-hit walk stops (at the first cell boundary beyond the hit), and a multi-hit walk
+ * has no such stop; no meaning is invented for it.  A device group is refused as for every query.
+ * Everything else as mrt_cast_rays_device: stream order and no host synchronisation; no allocation
+ * after a renderer's first query (the walk writes the caller's arrays itself: there is no staging
+ * buffer, and deviceBytes grows by the mapping tables only); chunks of rayCap[0]; the src mapping and the
+ * "no source" rule; state (later frames, views and queries keep their bits and counts, and the totals
+ * and frame statistics do not see the call).  Argument errors (a NULL handle, batch, orig, dir or out;
+ * K outside 1 .. MRT_MULTI_HITS_MAX; outSize too small to hold count; every field within outSize NULL;
+ * n or a stride as for mrt_cast_rays_device) return -1 before any device work, with a message in
+ * mrt_last_error(); they are checked before the renderer is read. */
+#define MRT_MULTI_HITS_MAX 16
+typedef struct mrt_multi_hits {   /* device arrays or NULL (not wanted); fields only ever appended */
+    int32_t *count;               /* n: the size of ray i's hit set */
+    int32_t *kind, *index;        /* n x K, ray i's entry k at i * K + k; values as mrt_cast_rays_device */
+    float   *t;                   /* n x K */
+    float   *bary;                /* n x K x 2: the walk's u, v for a triangle or a light, else 0, 0 */
+} mrt_multi_hits;
+
+int mrt_cast_multi_hits_device(mrt_renderer *r, const mrt_ray_batch *rays, int32_t K,
+                               const mrt_multi_hits *out, size_t outSize, void *stream);
 
 /* Host only (no GPU): the scene cfg names as the renderer holds it, every array in the scene's input
  * order - the order `index` and `material` of the ray queries refer to - and every float the exact

@@ -396,6 +396,64 @@ class Renderer:
                                   **{"d_" + name: x.data_ptr() for name, x in out.items()})
         return out
 
+    # -- multi-hit queries ---------------------------------------------------------------
+    MULTI_HIT_FIELDS = tuple(name for name, _, _ in _native.MULTI_HIT_FIELDS)
+
+    def cast_multi_hits_device(self, d_orig: int, d_dir: int, n: int, k: int, *, d_dist: int = 0, d_src: int = 0,
+                               orig_stride: int = 3, dir_stride: int = 3, d_count: int = 0, d_kind: int = 0,
+                               d_index: int = 0, d_t: int = 0, d_bary: int = 0, stream: int = 0,
+                               out_size: Optional[int] = None) -> None:
+        """mrt_cast_multi_hits_device: the first ``k`` (1 .. 16) hits along each of ``n`` rays resident in
+        device memory, in order, and each ray's hit count.  ``d_count`` (n int32), ``d_kind`` / ``d_index``
+        (n x k int32), ``d_t`` (n x k float32), ``d_bary`` (n x k x 2 float32): device pointers as ints to
+        packed arrays (mrt_multi_hits), 0: not wanted.  ``d_dist``: the rays' interval ends (n float32),
+        0: RayLengthMax.  ``out_size``: the bytes of the structure the library may read (None: all of
+        it).  Rays, ``d_src``, strides and ``stream`` as for cast_rays_device."""
+        out = _native.MrtMultiHits(d_count or None, d_kind or None, d_index or None, d_t or None, d_bary or None)
+        batch = _native.MrtRayBatch(d_orig or None, d_dir or None, d_dist or None, d_src or None, int(orig_stride),
+                                    int(dir_stride), int(n))
+        size = ctypes.sizeof(out) if out_size is None else int(out_size)
+        _native.check(self._lib.mrt_cast_multi_hits_device(self._h, ctypes.byref(batch), int(k), ctypes.byref(out), size,
+                                                           ctypes.c_void_p(stream or None)))
+
+    def cast_multi_hits(self, orig, dirs, k: int, dist=None, src=None, fields=None):
+        """cast_multi_hits_device for torch tensors on the renderer's device, with cast_rays' handling of
+        ``orig`` / ``dirs`` / ``src`` and its stream joining; ``dist`` float32 (n,) or None (RayLengthMax).
+        Returns a dict of tensors, one per name in ``fields`` (None: all of ``Renderer.MULTI_HIT_FIELDS``):
+        int32 ``count`` (n,), int32 ``kind`` / ``index`` (n, k), float32 ``t`` (n, k) and ``bary`` (n, k, 2),
+        allocated and ordered on torch's current stream.  An empty batch returns empty tensors."""
+        import torch
+
+        device, n, orig, orig_stride, dirs, dir_stride = self._ray_tensors(orig, dirs)
+        k = int(k)
+        if not 1 <= k <= _native.MULTI_HITS_MAX:
+            raise ValueError("k: 1 .. %d" % _native.MULTI_HITS_MAX)
+        fields = self.MULTI_HIT_FIELDS if fields is None else tuple(fields)
+        if not fields or any(f not in self.MULTI_HIT_FIELDS for f in fields):
+            raise ValueError("fields: at least one of %s" % (self.MULTI_HIT_FIELDS,))
+        if dist is not None:
+            if dist.device != device or dist.shape != (n,):
+                raise ValueError("dist: a tensor of shape (%d,) on %s" % (n, device))
+            dist = dist.to(torch.float32).contiguous()
+        if src is not None:
+            if src.device != device or src.shape != (n, 2):
+                raise ValueError("src: a tensor of shape (%d, 2) on %s" % (n, device))
+            src = src.to(torch.int32).contiguous()
+        out = {}
+        for name, dtype, width in _native.MULTI_HIT_FIELDS:
+            if name in fields:
+                shape = (n,) if width == 0 else (n, k) if width == 1 else (n, k, width)
+                out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=device)
+        if n == 0:
+            return out
+        with self._query_stream_of(device) as stream:
+            self.cast_multi_hits_device(orig.data_ptr(), dirs.data_ptr(), n, k,
+                                        d_dist=dist.data_ptr() if dist is not None else 0,
+                                        d_src=src.data_ptr() if src is not None else 0, orig_stride=orig_stride,
+                                        dir_stride=dir_stride, stream=stream,
+                                        **{"d_" + name: x.data_ptr() for name, x in out.items()})
+        return out
+
     def first_hit_planes(self, camera=None, sample: int = 0, fields=None):
         """The first hit of every pixel's camera ray (sample ``sample``) as planes: camera_rays(camera,
         sample_base=sample, spp=1), then cast_hits, scattered by ``pixels`` into (height, width) or

@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = (
     "mrt_get_queue_info", "mrt_plan_queues", "mrt_render_views", "mrt_render_views_device",
     "mrt_kat_accumulate", "mrt_cast_rays_device", "mrt_walk_stack", "mrt_plan_spill",
     "mrt_path_key", "mrt_shade_rays_device", "mrt_camera_rays_device",
-    "mrt_cast_hits_device", "mrt_scene_triangles", "mrt_scene_planes", "mrt_scene_spheres", "mrt_scene_materials",
+    "mrt_cast_hits_device", "mrt_cast_multi_hits_device", "mrt_scene_triangles", "mrt_scene_planes", "mrt_scene_spheres", "mrt_scene_materials",
     "mrt_scene_lights",
     "RayTrace", "stopRender",
 )
@@ -75,6 +75,17 @@ HIT_FIELDS = (("kind", "int32", 1), ("index", "int32", 1), ("t", "float32", 1), 
 
 class MrtHitRecords(ctypes.Structure):  # mrt_hit_records: device arrays of a surface-record query, NULL = not wanted
     _fields_ = [(name, ctypes.c_void_p) for name, _, _ in HIT_FIELDS]
+
+
+MULTI_HITS_MAX = 16  # MRT_MULTI_HITS_MAX
+# mrt_multi_hits: the fields in the header's order, (name, dtype, entries per ray: 0 = one per ray, else
+# floats or ints per list entry)
+MULTI_HIT_FIELDS = (("count", "int32", 0), ("kind", "int32", 1), ("index", "int32", 1), ("t", "float32", 1),
+                    ("bary", "float32", 2))
+
+
+class MrtMultiHits(ctypes.Structure):  # mrt_multi_hits: device arrays of a multi-hit query, NULL = not wanted
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in MULTI_HIT_FIELDS]
 
 
 class MrtShadeBatch(ctypes.Structure):  # mrt_shade_batch: rays and their path keys (mrt_shade_rays_device)
@@ -220,6 +231,8 @@ def load_library(path=LIB_PATH):
         "mrt_trace_rays": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]),
         "mrt_cast_rays_device": (ctypes.c_int, [vp, P(MrtRayBatch), ctypes.c_int32, vp, vp, vp, vp]),
         "mrt_cast_hits_device": (ctypes.c_int, [vp, P(MrtRayBatch), P(MrtHitRecords), ctypes.c_size_t, vp]),
+        "mrt_cast_multi_hits_device": (ctypes.c_int, [vp, P(MrtRayBatch), ctypes.c_int32, P(MrtMultiHits),
+                                                      ctypes.c_size_t, vp]),
         "mrt_scene_triangles": (ctypes.c_int64, [vp, vp, vp, vp, vp]),
         "mrt_scene_planes": (ctypes.c_int64, [vp, vp, vp]),
         "mrt_scene_spheres": (ctypes.c_int64, [vp, vp, vp]),
@@ -255,7 +268,7 @@ def source_stamp():
     srcs = ["mrt_scene.cpp", "mrt_grid.cpp", "mrt_texture.cpp", "mrt_android.cpp", "mrt_queue_plan.cpp", "mrt_kernels.hip",
             "mrt_renderer.hip",
             "mrt_common.hpp", "mrt_device.hpp", "mrt_kernels.hpp", "mrt_trace_ww.hpp", "mrt_trace_packet.hpp",
-            "mrt_scene.hpp", "mrt_queue_plan.hpp", "../../include/mobilert_amd.h", "../../include/mobilert_amd.hpp",
+            "mrt_multi_hit.hpp", "mrt_scene.hpp", "mrt_queue_plan.hpp", "../../include/mobilert_amd.h", "../../include/mobilert_amd.hpp",
             "../../include/mobilert_android.h"]
     h = hashlib.sha256()
     for f in srcs:

@@ -19,6 +19,7 @@
 #include "mrt_kernels.hpp"
 #include "mrt_trace_ww.hpp"
 #include "mrt_trace_packet.hpp"
+#include "mrt_multi_hit.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1537,6 +1538,77 @@ void launchShadeLoad(const Level& lv, const QueryRays& q, const QueryTables& tb,
                      int* counters, hipStream_t st) {
     hipLaunchKernelGGL(k_query_load<true>, dim3(std::max(1, (n + 255) / 256)), dim3(256), 0, st, lv, q, tb, n, 0,
                        counters, keys);
+}
+
+// ---------------------------------------------------------------------------------------
+// Multi-hit queries (mrt_cast_multi_hits_device).  k_multi_walk: a per-lane walk, one ray per lane, a
+// wave taking 64 rays at a time from level 1's fetch cursor as k_trace's variant 0 does, each lane
+// keeping its first K hits in an LDS K-buffer (mrt_multi_hit.hpp) and writing the caller's arrays
+// itself when its ray is done: no staging buffer, no store kernel.  The wave's 64 rays are adjacent
+// (level 1 is dense), so count is one coalesced store and entry k of kind / index / t a store of
+// stride K dwords; entries count .. K - 1 are written as padding (kind 0, index -1, t = tmax, bary 0, 0).
+// kCeil: the K-buffer's size in LDS (1, 4 or 16 entries of 16 B per lane) - with the 64 B of stack
+// per lane 5, 8 and 20 KB per one-wave workgroup, which bounds the occupancy: 7, 5 and 2 waves per
+// SIMD (at K = 16 eight workgroups in a CU's 160 KB).
+template <int kCeil>
+__global__ __launch_bounds__(kMultiThreads) void k_multi_walk(DScene s, Level lv, int* counters, int2* gstack, int gdepth,
+                                                              QueryTables tb, const float* dist, long long base, int K,
+                                                              MultiHits out) {
+    __shared__ int ldsStack[RefStack<kMultiThreads>::kDepth * kMultiThreads];
+    __shared__ float kbT[kCeil * kMultiThreads];
+    __shared__ uint32_t kbCode[kCeil * kMultiThreads];
+    __shared__ float kbU[kCeil * kMultiThreads];
+    __shared__ float kbV[kCeil * kMultiThreads];
+    auto st = makeRefStack<kMultiThreads>(reinterpret_cast<int2*>(ldsStack), gstack, gdepth);
+    KBuffer kb{kbT + threadIdx.x, kbCode + threadIdx.x, kbU + threadIdx.x, kbV + threadIdx.x, min(K, kCeil), 0, 0, 0.0F};
+    const SegMap map = segMap(counters, 1, false, lv.segCap);
+    int* fetch = counters + kCntFetchShards + 1 * kMaxFetchShards * kFetchStride;
+    while (true) {
+        int first = 0;
+        if (laneId() == 0) first = atomicAdd(fetch, 64);
+        first = __shfl(first, 0, 64);
+        if (first >= map.total()) break;
+        const int v = first + laneId();
+        if (v < map.total()) {
+            const int i = map.phys(v);
+            const long long g = base + i;  // the ray's index in the caller's batch (k_query_load put it at i)
+            const float4 o4 = lv.rO[i];
+            const float4 d4 = lv.rD[i];
+            kb.reset(dist != nullptr ? dist[g] : kRayLengthMax);
+            multiHits(s, xyz(o4), xyz(d4), fbits(d4.w), kb, st);
+            if (out.count != nullptr) out.count[g] = kb.count;
+            const long long e0 = g * K;
+            for (int k = 0; k < kb.K; ++k) {
+                const bool held = k < kb.n;
+                const uint32_t code = held ? kb.code[k * kMultiThreads] : kNoPrim;
+                const uint32_t kind = primKind(code);
+                if (out.kind != nullptr) out.kind[e0 + k] = static_cast<int32_t>(kind);
+                if (out.index != nullptr) {
+                    const int32_t* order = kind == kTriangle ? tb.triOrder : kind == kPlane ? tb.planeOrder : kind == kSphere ? tb.sphereOrder : nullptr;
+                    const int32_t b = static_cast<int32_t>(primIndex(code));
+                    out.index[e0 + k] = !held ? -1 : order != nullptr ? order[b] : b;  // (lights keep their input order)
+                }
+                if (out.t != nullptr) out.t[e0 + k] = held ? kb.t[k * kMultiThreads] : kb.tmax;
+                if (out.bary != nullptr) {
+                    out.bary[2 * (e0 + k)] = held ? kb.u[k * kMultiThreads] : 0.0F;
+                    out.bary[2 * (e0 + k) + 1] = held ? kb.v[k * kMultiThreads] : 0.0F;
+                }
+            }
+        }
+    }
+}
+
+void launchMultiWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth, const QueryTables& tb,
+                     const float* dist, long long base, int n, int K, const MultiHits& out, int maxThreads,
+                     hipStream_t st) {
+    // a persistent grid over the fetch cursor: a wave per 64 rays, at most the threads the spill area holds
+    const dim3 blocks(std::max(1, std::min(maxThreads / kMultiThreads, (n + kMultiThreads - 1) / kMultiThreads)));
+#define MRT_LAUNCH_MULTI(CEIL) \
+    hipLaunchKernelGGL(k_multi_walk<CEIL>, blocks, dim3(kMultiThreads), 0, st, s, lv, counters, gstack, gdepth, tb, dist, base, K, out)
+    if (K <= 1) MRT_LAUNCH_MULTI(1);
+    else if (K <= 4) MRT_LAUNCH_MULTI(4);
+    else MRT_LAUNCH_MULTI(kMultiHitsMax);
+#undef MRT_LAUNCH_MULTI
 }
 
 // ---------------------------------------------------------------------------------------

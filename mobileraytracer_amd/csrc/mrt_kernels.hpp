@@ -332,6 +332,24 @@ struct HitRecords {
 // point: no shading or material record is fetched) where out.beyondGeometry() is false, else the full one.
 void launchQueryStoreHits(const DScene& s, const Level& lv, const QueryTables& tb, int n, long long base,
                           const HitRecords& out, hipStream_t st);
+// Multi-hit queries (mrt_cast_multi_hits_device): the device arrays of mrt_multi_hits, packed (ray g's
+// count at g, its entry k at g * K + k, two floats per entry of bary) or null (not wanted: not stored).
+constexpr int kMultiHitsMax = 16;  // MRT_MULTI_HITS_MAX: the largest K-buffer
+struct MultiHits {
+    int32_t* count;
+    int32_t* kind;
+    int32_t* index;
+    float* t;
+    float* bary;
+};
+// k_multi_walk (mrt_multi_hit.hpp): the n rays k_query_load put into lv's queue walked with no cull,
+// each ray's first K hits (K 1 .. 16) in order, its hit count and the padding stored by the walk itself
+// at base + i, indices mapped to input order through tb.  dist: the caller's tmax array (ray base + i's
+// at dist[base + i]) or null (RayLengthMax).  The spill area is the closest-hit walk's (gstack, gdepth
+// entries for each of maxThreads threads): the grid holds at most maxThreads threads.
+void launchMultiWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth, const QueryTables& tb,
+                     const float* dist, long long base, int n, int K, const MultiHits& out, int maxThreads,
+                     hipStream_t st);
 // Shaded ray queries (mrt_shade_rays_device).  k_query_load's keyed form: n rays of q into lv's queue
 // as level-1 records of a frame's kind - rO.w the path key (keys[base + i]; null: pathKey(base + i, 0)),
 // rD.w the mapped source, tree = 1 - with the dense segment counts.

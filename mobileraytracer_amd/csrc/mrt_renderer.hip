@@ -1925,6 +1925,71 @@ mrt::QueryRays checkHitBatch(const mrt_renderer* r, const mrt_ray_batch* rays, c
     return q;
 }
 
+// ---- multi-hit queries (mrt_cast_multi_hits_device) --------------------------------------------
+// The argument checks, all before any device work, the batch, K and the outputs before the renderer
+// is read; fills the batch with its strides resolved (dist kept: the optional tmax) and the outputs:
+// the first outSize bytes of *out, whole fields only, every field beyond them null.
+mrt::QueryRays checkMultiBatch(const mrt_renderer* r, const mrt_ray_batch* rays, int32_t K, const mrt_multi_hits* out,
+                               size_t outSize, mrt::MultiHits* mh) {
+    if (r == nullptr) throw std::runtime_error("mrt_cast_multi_hits_device: null renderer");
+    if (rays == nullptr) throw std::runtime_error("mrt_cast_multi_hits_device: null ray batch");
+    if (rays->orig == nullptr || rays->dir == nullptr) throw std::runtime_error("mrt_cast_multi_hits_device: null orig / dir");
+    if (out == nullptr) throw std::runtime_error("mrt_cast_multi_hits_device: null multi hits");
+    if (K < 1 || K > MRT_MULTI_HITS_MAX)
+        throw std::runtime_error("mrt_cast_multi_hits_device: K must be 1 .. " + std::to_string(MRT_MULTI_HITS_MAX));
+    static_assert(MRT_MULTI_HITS_MAX == mrt::kMultiHitsMax, "the K-buffer's largest instantiation holds the header's K");
+    if (outSize < offsetof(mrt_multi_hits, count) + sizeof(out->count))
+        throw std::runtime_error("mrt_cast_multi_hits_device: outSize too small to hold count");
+    static_assert(sizeof(mrt_multi_hits) == 5 * sizeof(void*), "mrt_multi_hits: pointers only (fields are appended)");
+    mrt_multi_hits o{};
+    std::memcpy(&o, out, std::min(outSize, sizeof(o)) / sizeof(void*) * sizeof(void*));
+    *mh = mrt::MultiHits{o.count, o.kind, o.index, o.t, o.bary};
+    if (o.count == nullptr && o.kind == nullptr && o.index == nullptr && o.t == nullptr && o.bary == nullptr)
+        throw std::runtime_error("mrt_cast_multi_hits_device: no output (every field within outSize is null)");
+    if (rays->n < 1 || rays->n > 0x7fffffffLL) throw std::runtime_error("mrt_cast_multi_hits_device: n must be 1 .. 2^31 - 1");
+    auto stride = [](int64_t s, const char* name) -> long long {
+        if (s == 0) return 3;
+        if (s < 3) throw std::runtime_error(std::string("mrt_cast_multi_hits_device: ") + name + " must be 0 (packed) or >= 3 floats");
+        return s;
+    };
+    mrt::QueryRays q{};
+    q.orig = rays->orig;
+    q.dir = rays->dir;
+    q.dist = rays->dist;
+    q.src = rays->src;
+    q.origStride = stride(rays->origStride, "origStride");
+    q.dirStride = stride(rays->dirStride, "dirStride");
+    if (!r->peers.empty()) throw std::runtime_error("mrt_cast_multi_hits_device: device groups are not supported for ray queries");
+    if (r->ds.accel == mrt::kAccGrid)
+        throw std::runtime_error("mrt_cast_multi_hits_device: the RegularGrid accelerator (2) is not supported: its visit set "
+                                 "depends on where the closest-hit walk stops");
+    return q;
+}
+
+// castRays' chunk loop with the multi-hit walk in the walk's place and no store kernel: the rays go
+// into level 1's queue as a closest-hit query's (k_query_load), k_multi_walk writes the caller's arrays.
+void castMultiHits(mrt_renderer* r, mrt::QueryRays q, int64_t n, int K, const mrt::MultiHits& out) {
+    using namespace mrt;
+    hipStream_t st = r->stream;
+    const QueryTables& tb = queryTables(r);
+    mrt_renderer::Pipe& pp = r->pipe;
+    const Level& lv = pp.levels[1];  // (the plan in use now, as castRays)
+    const int64_t cap = std::min<int64_t>(lv.cap, static_cast<int64_t>(kQueueSegs) * lv.segCap);
+    if (cap <= 0) throw std::runtime_error("mrt_cast_multi_hits_device: the level-1 queue holds no rays");
+    const int walkThreads = r->walkGridCap > 0 ? std::min(r->traceThreads, r->walkGridCap * kBlock) : r->traceThreads;
+    const float* dist = q.dist;
+    q.dist = nullptr;  // (the load is the closest-hit form's: it reads no dist)
+    for (int64_t base = 0; base < n; base += cap) {
+        const int m = static_cast<int>(std::min<int64_t>(cap, n - base));
+        q.base = base;
+        MRT_HIP(hipMemsetAsync(pp.counters, 0, sizeof(int) * kNumCounters, st));
+        r->countersClean = false;  // (left in use: the next pass resets them)
+        launchQueryLoad(lv, q, tb, m, false, pp.counters, st);
+        launchMultiWalk(r->ds, lv, pp.counters, pp.gstack, r->gdepth, tb, dist, base, m, K, out, walkThreads, st);
+    }
+    MRT_HIP(hipGetLastError());
+}
+
 // ---- shaded ray queries (mrt_shade_rays_device) ------------------------------------------------
 // The argument checks, all before any device work, in checkRayBatch's order: the batch and the
 // output first (those checks do not read the renderer).
@@ -2203,6 +2268,26 @@ int mrt_cast_hits_device(mrt_renderer* r, const mrt_ray_batch* rays, const mrt_h
         }
         // nothing beyond kind / index / t wanted: the hit query's own store kernel
         castRays(r, q, rays->n, false, rec.kind, rec.index, rec.t, rec.beyondHit() ? &rec : nullptr);
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinOut, r->stream));
+            MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
+        }
+    });
+}
+
+int mrt_cast_multi_hits_device(mrt_renderer* r, const mrt_ray_batch* rays, int32_t K, const mrt_multi_hits* out,
+                               size_t outSize, void* stream) {
+    return guarded([&] {
+        mrt::MultiHits mh{};
+        const mrt::QueryRays q = checkMultiBatch(r, rays, K, out, outSize, &mh);
+        MRT_HIP(hipSetDevice(r->device));
+        hipStream_t st = stream != nullptr ? static_cast<hipStream_t>(stream) : r->stream;
+        // joined to the caller's stream on both sides, as mrt_cast_rays_device
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinIn, st));
+            MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
+        }
+        castMultiHits(r, q, rays->n, K, mh);
         if (st != r->stream) {
             MRT_HIP(hipEventRecord(r->joinOut, r->stream));
             MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));

@@ -160,4 +160,5 @@ def main():
     return 0 if min(ratios) >= 1.0 else 1
 
 
-sys.exit(main())
+if __name__ == "__main__":  # (tools/multi_hit_bench.py imports the ray generators)
+    sys.exit(main())
