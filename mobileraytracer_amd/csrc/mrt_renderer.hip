@@ -129,7 +129,7 @@ std::vector<mrt::HBVHNode> frameWalkTree(const std::vector<mrt::HBVHNode>& wn, c
         f.pod(l.tri.AC);
     }
     f.pod(cam);
-    const int dims[4] = {width, height, maxDepth, sweeps};
+    const int dims[4] = {width, height, std::min(maxDepth, mrt::kSampleDepthMax), sweeps};  // (what the sample reads)
     f.pod(dims);
     using Entry = std::shared_ptr<const FrameTree>;
     static std::mutex mu;
@@ -386,6 +386,8 @@ struct mrt_renderer {
     int deviceShare = 1;                 // shards of the device group on this renderer's GPU (the budget's divisor)
     bool planStale = false;              // a key above changed: first allocation again before the next pass
     int64_t replans = 0, replansFrame = 0;  // plans made after an overflowed pass: ever, this frame
+    bool planFromDemand = false;         // the plan was made from a pass's demand (else: a first allocation)
+    bool planTight = false;              // a first allocation held the last pass with little room (runPass)
     // the last pass's demand record (k_tally's kStatReq*): per level the largest segment's count and
     // the total, for rays and shadow rays; the overflow mask; the paths of its (largest) chunk
     int64_t reqSegRays[mrt::kMaxLevels] = {}, reqSegShadows[mrt::kMaxLevels] = {};
@@ -975,19 +977,18 @@ void adoptPlan(mrt_renderer* r, mrt_queue_plan_request q) {
     r->planSlots = q.pixelSlots;
     r->planSpp = q.samplesPixel;
     r->planStale = false;
+    r->planTight = false;
+    r->planFromDemand = q.hasDemand != 0 || q.worstCase != 0;
     allocQueues(r);
 }
 
 // The first allocation.
 void planFirst(mrt_renderer* r) { adoptPlan(r, planRequest(r)); }
 
-// After an overflowed pass (runPass kept its demand record): demand-driven plans for the first
-// kPlanDemandRetries retries of a frame, then the worst-case plan, which cannot overflow.
-void planAfterOverflow(mrt_renderer* r, int retry) {
+// The request for a plan from the last pass's demand record (runPass kept it).
+mrt_queue_plan_request demandRequest(mrt_renderer* r) {
     using namespace mrt;
-    if (r->plan.worstCase != 0) throw std::runtime_error("wavefront queue overflow under the worst-case queue plan");
     mrt_queue_plan_request q = planRequest(r);
-    q.worstCase = retry >= kPlanDemandRetries ? 1 : 0;
     q.hasDemand = 1;
     q.overflowMask = r->overflowMask;
     q.demandChunkSlots = r->plan.chunkSlots;
@@ -999,6 +1000,31 @@ void planAfterOverflow(mrt_renderer* r, int retry) {
         q.prevSegCap[l] = r->plan.segCap[l];
         q.prevShadowSegCap[l] = r->plan.shadowSegCap[l];
     }
+    return q;
+}
+
+// After a pass that a first allocation held with little room (runPass set planTight): the queues
+// planned from that pass's demand, every level of it exact, as after an overflow - but no pass is
+// redone and nothing is counted as a replan.  Kept out where the plan would shrink the chunk (the
+// byte budget): the first allocation stays, and an overflow is handled as ever.
+void planForHeadroom(mrt_renderer* r) {
+    using namespace mrt;
+    r->planTight = false;
+    mrt_queue_plan_request q = demandRequest(r);
+    q.overflowMask = 1 << r->nLevels;  // (no level dropped a write: the planner takes every level as exact)
+    std::string err;
+    mrt_queue_plan plan{};
+    if (!planQueues(q, &plan, &err) || plan.chunkSlots != r->plan.chunkSlots) return;
+    adoptPlan(r, q);
+}
+
+// After an overflowed pass (runPass kept its demand record): demand-driven plans for the first
+// kPlanDemandRetries retries of a frame, then the worst-case plan, which cannot overflow.
+void planAfterOverflow(mrt_renderer* r, int retry) {
+    using namespace mrt;
+    if (r->plan.worstCase != 0) throw std::runtime_error("wavefront queue overflow under the worst-case queue plan");
+    mrt_queue_plan_request q = demandRequest(r);
+    q.worstCase = retry >= kPlanDemandRetries ? 1 : 0;
     adoptPlan(r, q);
     ++r->replans;
     ++r->replansFrame;
@@ -1264,7 +1290,11 @@ bool runPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t st
     // (tuning keys 37-39 changed; or the slot count did, between a frame and a batch of views: the
     // chunk is sized for the range the pass runs over, and a plan learned for the other count is dropped)
     // (... or a shade batch came or went: its slots are single paths)
-    if (r->planStale || r->planSlots != std::max<int64_t>(1, passSlots(r)) || r->planSpp != passSpp(r)) planFirst(r);
+    if (r->planStale || r->planSlots != std::max<int64_t>(1, passSlots(r)) || r->planSpp != passSpp(r)) {
+        planFirst(r);
+    } else if (r->planTight) {
+        planForHeadroom(r);
+    }
     const auto t0 = std::chrono::steady_clock::now();
     renderPass(r, dBitmap, dPacked, st, sampleBase, spp);
     MRT_HIP(hipStreamSynchronize(st));  // (k_tally wrote the pass's statistics into r->hostStats)
@@ -1281,6 +1311,19 @@ bool runPass(mrt_renderer* r, int32_t* dBitmap, int32_t* dPacked, hipStream_t st
     r->overflowMask = static_cast<int>(hs[kStatOverflow]);
     r->reqPaths = std::min<int64_t>(r->chunkSlots, std::max<int64_t>(1, passSlots(r))) * spp;
     if (hs[kStatOverflow] != 0) return false;
+    // A first allocation held this pass.  With little room it need not hold the next one: which
+    // vertices share a 256-vertex block, and so a queue segment, varies from run to run with the order
+    // their level was queued in, and the segment's demand with it (level 1 is dense: its shadow rays'
+    // segments are the same every time).  Where a deeper segment's demand came within the planner's
+    // own margin (1.25 x the demand), the next pass starts with queues planned from this demand, so
+    // that a frame which fitted is not followed by one that is redone (glassboxes 16 x 16, Whitted,
+    // maxDepth 7: 7997 shadow rays of level 7 in queues of 8 x 1104, which held one frame and not the next).
+    // (Not the last level: its rays are counted whether or not they are written, and it has no shadow rays.)
+    if (!r->planFromDemand) {
+        for (int l = 1; l + 1 < r->nLevels; ++l)
+            r->planTight = r->planTight || 5 * r->reqSegRays[l] > 4 * r->plan.segCap[l] ||
+                           5 * r->reqSegShadows[l] > 4 * r->plan.shadowSegCap[l];
+    }
     fs->rays += hs[kStatRays];
     fs->shadowRays += hs[kStatShadowRays];
     fs->walkedRays += hs[kStatRays] - hs[kStatSkipped];

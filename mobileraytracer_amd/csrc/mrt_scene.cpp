@@ -1850,6 +1850,7 @@ std::vector<SampleRay> sampleFrameRays(const std::vector<HBVHNode>& nodes, const
     using Ray = SampleRay;
     std::vector<Ray> rays;
     if (nodes.empty() || sc.triangles.empty()) return rays;
+    maxDepth = std::min(maxDepth, kSampleDepthMax);
     auto inner = [&](size_t i) { return nodes[i].numPrimitives == 0 && nodes.size() > 1; };
     const auto entry = halfLineEntry;
     auto triHit = [](const HTriangle& t, v3 o, v3 d, float* tOut) {  // Moller-Trumbore, float

@@ -168,6 +168,10 @@ struct SampleRay {
     v3 o, d;
     float w;
 };
+// The sample follows the paths to min(maxDepth, kSampleDepthMax): it doubles per level where every hit
+// reflects (glassboxes at maxDepth 13: 23 s of host time per renderer against 1.4 s at 6), and what it
+// feeds is a cost estimate, tuned at the default depth, that leaves every walk exact.
+constexpr int kSampleDepthMax = 6;  // RayDepthMax (Constants.hpp:45)
 std::vector<SampleRay> sampleFrameRays(const std::vector<HBVHNode>& nodes, const HScene& sc, const GCamera& cam,
                                        int maxDepth);
 // frameRayNodeCosts over a given sample

@@ -1782,28 +1782,30 @@ void oracle_primary_hits(void* h, int32_t* kind, int32_t* index, float* t) {
     }
 }
 
+// the primitive a (kind, input index) source pair names (Ray::primitive_), NULL where it names none
+static const void* findSource(const oracle::Engine* e, int32_t k, int32_t j) {
+    if (k == 3) {
+        for (const auto& p : e->triangles->primitives) if (p.inputIndex == j) return &p;
+    } else if (k == 1) {
+        for (const auto& p : e->planes->primitives) if (p.inputIndex == j) return &p;
+    } else if (k == 2) {
+        for (const auto& p : e->spheres->primitives) if (p.inputIndex == j) return &p;
+    } else if (k == 4) {
+        for (const auto& l : e->lights) if (l.index == j) return &l.triangle;
+    }
+    return nullptr;
+}
+
 // Shader::rayTrace's intersection part (any = 0: kind / input index / t) or Shader::shadowTrace
 // (any = 1, tmax dist[i]: kind[i] = occluded) of arbitrary rays; src: NULL or (kind, input
 // index) pairs of the primitive each ray leaves (Ray::primitive_, self-exclusion)
 void oracle_trace_rays(void* h, const float* o, const float* d, const float* dist, const int32_t* src, int32_t n,
                        int any, int32_t* kind, int32_t* index, float* t) {
     auto* e = static_cast<oracle::Engine*>(h);
-    auto find = [&](int32_t k, int32_t j) -> const void* {
-        if (k == 3) {
-            for (const auto& p : e->triangles->primitives) if (p.inputIndex == j) return &p;
-        } else if (k == 1) {
-            for (const auto& p : e->planes->primitives) if (p.inputIndex == j) return &p;
-        } else if (k == 2) {
-            for (const auto& p : e->spheres->primitives) if (p.inputIndex == j) return &p;
-        } else if (k == 4) {
-            for (const auto& l : e->lights) if (l.index == j) return &l.triangle;
-        }
-        return nullptr;
-    };
     for (int32_t i = 0; i < n; ++i) {
         const oracle::Vec3 org(o[3 * i], o[3 * i + 1], o[3 * i + 2]);
         const oracle::Vec3 dir(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
-        const void* prim = src != nullptr ? find(src[2 * i], src[2 * i + 1]) : nullptr;
+        const void* prim = src != nullptr ? findSource(e, src[2 * i], src[2 * i + 1]) : nullptr;
         if (any) {
             const oracle::Ray ray(dir, org, 2, true, prim, nullptr);
             kind[i] = e->shadowTrace(dist[i], ray) ? 1 : 0;
@@ -1819,6 +1821,66 @@ void oracle_trace_rays(void* h, const float* o, const float* d, const float* dis
             t[i] = it.length;
         }
     }
+}
+
+// Shader::rayTrace's `rgb` for arbitrary rays, before any conversion: ray i is the depth-1 ray of a
+// path with key keys[i] (NULL: pathKey(i, 0)), src as for oracle_trace_rays.  With threads the rays
+// are split statically, each worker on its own copy of the materials (as renderTiles' workers).
+// Returns the rays cast by this call, the given ones included (a frame counts its camera rays).
+uint64_t oracle_shade_rays(void* h, const float* o, const float* d, const uint32_t* keys, const int32_t* src, int32_t n,
+                           int threads, float* rgb) {
+    auto* e = static_cast<oracle::Engine*>(h);
+    const uint64_t before = e->rays.load();
+    const int nThreads = std::max(1, std::min(threads, n));
+    auto worker = [&](int32_t first, int32_t last) {
+        std::vector<oracle::Material> mats = e->materials;
+        for (int32_t i = first; i < last; ++i) {
+            const oracle::Vec3 org(o[3 * i], o[3 * i + 1], o[3 * i + 2]);
+            const oracle::Vec3 dir(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+            const void* prim = src != nullptr ? findSource(e, src[2 * i], src[2 * i + 1]) : nullptr;
+            const uint32_t key = keys != nullptr ? keys[i] : oracle::pathKey(static_cast<uint32_t>(i), 0u);
+            const oracle::Ray ray(dir, org, 1, false, prim, &e->rays);
+            oracle::Vec3 out;
+            e->rayTrace(&out, ray, oracle::Engine::Ctx{key, &mats}, 1u);
+            for (int a = 0; a < 3; ++a) rgb[3 * i + a] = out[a];
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nThreads; ++t)
+        pool.emplace_back(worker, static_cast<int32_t>(static_cast<int64_t>(n) * t / nThreads),
+                          static_cast<int32_t>(static_cast<int64_t>(n) * (t + 1) / nThreads));
+    worker(0, static_cast<int32_t>(static_cast<int64_t>(n) / nThreads));
+    for (auto& t : pool) t.join();
+    return e->rays.load() - before;
+}
+
+// the frame's camera rays (Engine::cameraRay): tiles in order, the pixels of a tile row by row,
+// samples sampleBase .. sampleBase + spp - 1 innermost; only pixels with idx < W * H.  Returns the
+// count; with o == NULL nothing is written.
+int64_t oracle_camera_rays(void* h, int sampleBase, int spp, float* o, float* d, uint32_t* keys, int32_t* pixels) {
+    auto* e = static_cast<oracle::Engine*>(h);
+    const int W = e->cfg.width, H = e->cfg.height, bx = W / 16, by = H / 16;
+    int64_t n = 0;
+    for (const auto& tile : e->tiles()) {
+        for (int y = tile[1]; y < tile[1] + by; ++y) {
+            for (int x = tile[0]; x < tile[0] + bx; ++x) {
+                const int64_t idx = static_cast<int64_t>(y) * W + x;
+                if (idx >= static_cast<int64_t>(W) * H) continue;
+                for (int s = sampleBase; s < sampleBase + spp; ++s, ++n) {
+                    if (o == nullptr) continue;
+                    uint32_t key;
+                    const oracle::Ray ray = e->cameraRay(x, y, s, &key);
+                    for (int a = 0; a < 3; ++a) {
+                        o[3 * n + a] = ray.origin[a];
+                        d[3 * n + a] = ray.direction[a];
+                    }
+                    keys[n] = key;
+                    pixels[n] = static_cast<int32_t>(idx);
+                }
+            }
+        }
+    }
+    return n;
 }
 
 // reference-numbered BVH of the triangles: boxes (n x 6), indexOffset, numPrimitives, prim order

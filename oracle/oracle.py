@@ -48,6 +48,10 @@ def lib():
         L.oracle_counts.argtypes = [vp, vp]
         L.oracle_primary_hits.argtypes = [vp, vp, vp, vp]
         L.oracle_trace_rays.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int, vp, vp, vp]
+        L.oracle_shade_rays.restype = ctypes.c_uint64
+        L.oracle_shade_rays.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int, vp]
+        L.oracle_camera_rays.restype = ctypes.c_int64
+        L.oracle_camera_rays.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
         L.oracle_triangle_bvh.restype = ctypes.c_int64
         L.oracle_triangle_bvh.argtypes = [vp, vp, vp, vp, vp]
         L.oracle_kat_triangle.argtypes = [f, f, f, f, f, ctypes.c_int, f]
@@ -186,7 +190,7 @@ class Oracle:
 
     def __init__(self, width, height, shader=1, sceneIndex=0, samplesPixel=1, samplesLight=1, maxDepth=6,
                  obj="", mtl="", cam="", accelerator=3):
-        self.width, self.height = width, height
+        self.width, self.height, self.samples_pixel = width, height, samplesPixel
         self._keep = [s.encode() for s in (obj, mtl, cam)]
         if obj:
             register_textures(obj, mtl)
@@ -240,6 +244,35 @@ class Oracle:
                                 None if sp is None else sp.ctypes.data, n, int(any_hit),
                                 k.ctypes.data, i.ctypes.data, t.ctypes.data)
         return k, i, t
+
+    def shade_rays(self, orig, dirs, keys=None, src=None, threads=1):
+        """Shader::rayTrace's rgb, before any conversion, of arbitrary rays: (rgb float32 (n, 3), rays
+        cast).  Ray i is the depth-1 ray of a path with key keys[i] (None: path_key(i, 0)); src as for
+        trace_rays.  The count includes the n given rays, as a frame's includes its camera rays."""
+        o = np.ascontiguousarray(orig, np.float32)
+        d = np.ascontiguousarray(dirs, np.float32)
+        n = len(o)
+        assert o.shape == (n, 3) and d.shape == (n, 3)
+        ks = None if keys is None else np.ascontiguousarray(keys).astype(np.int64).astype(np.uint32)
+        sp = None if src is None else np.ascontiguousarray(src, np.int32)
+        assert (ks is None or ks.shape == (n,)) and (sp is None or sp.shape == (n, 2))
+        rgb = np.zeros((n, 3), np.float32)
+        casts = lib().oracle_shade_rays(self._h, o.ctypes.data, d.ctypes.data, None if ks is None else ks.ctypes.data,
+                                        None if sp is None else sp.ctypes.data, n, int(threads), rgb.ctypes.data)
+        return rgb, int(casts)
+
+    def camera_rays(self, sample_base=0, spp=None):
+        """The frame's camera rays (the engine's cameraRay) as (orig (n, 3), dirs (n, 3) float32, keys
+        uint32, pixels int32): tiles in order, the pixels of a tile, samples sample_base ..
+        sample_base + spp - 1 innermost (spp None: samplesPixel).  A pixel that two tiles cover
+        appears once per tile."""
+        spp = int(spp) if spp else max(1, self.samples_pixel)
+        n = lib().oracle_camera_rays(self._h, int(sample_base), spp, None, None, None, None)
+        o, d = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+        keys, pixels = np.empty(n, np.uint32), np.empty(n, np.int32)
+        lib().oracle_camera_rays(self._h, int(sample_base), spp, o.ctypes.data, d.ctypes.data, keys.ctypes.data,
+                                 pixels.ctypes.data)
+        return o, d, keys, pixels
 
     def triangle_bvh(self):
         n = lib().oracle_triangle_bvh(self._h, None, None, None, None)
