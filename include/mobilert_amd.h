@@ -24,6 +24,10 @@
  *                             the first K hits along each of the caller's rays, in order, and the hit count:
  *                             every hit Shader::rayTrace's intersection part would accept on an unshortened
  *                             ray (no single reference call)
+ *   mrt_nearest_points_device
+ *                             the nearest surface to each of the caller's points: which primitive, the squared
+ *                             distance, the point on it and its barycentrics (no reference call: the reference
+ *                             answers questions about rays only); mrt_point_distance is its definition on the host
  *   mrt_scene_triangles / _planes / _spheres / _materials / _lights
  *                             Shader::getTriangles / getPlanes / getSpheres / getMaterials / getLights
  *                             (Shader.hpp:92-100) in the scene's input order
@@ -586,6 +590,71 @@ int64_t mrt_scene_planes(const mrt_config *cfg, float *normalPoint, int32_t *mat
 int64_t mrt_scene_spheres(const mrt_config *cfg, float *centreSqRadius, int32_t *material);
 int64_t mrt_scene_materials(const mrt_config *cfg, float *coeffs, int32_t *texture);
 int64_t mrt_scene_lights(const mrt_config *cfg, int32_t *kind, float *geom, float *coeffs);
+
+/* ---- nearest-point queries (on the GPU; beyond the reference's entry points) ----
+ * mrt_nearest_points_device: for each point of a caller-supplied batch the nearest surface of the loaded
+ * scene: clearance and collision margins, snapping a point to the mesh, distance fields, the thickness
+ * under a surface point - without casting many rays and hoping.
+ *
+ * The distance functions (mrt_point_distance evaluates them on the host; the kernels compile the same
+ * source without contraction, so the bits agree).  Each gives d2 (squared distance, float32), the nearest
+ * point q and for triangles the barycentrics u, v (the weights of B and C):
+ *   triangle (A, AB, AC as mrt_scene_triangles holds them; an area light's A, AB, AC likewise): Ericson's
+ *     closest point on a triangle by Voronoi regions, then ALWAYS u = min(max(u, 0), 1),
+ *     v = min(max(v, 0), 1 - u) (NaN -> 0), q = (A + AB * u) + AC * v, d2 = |p - q|^2 summed (x + y) + z.
+ *     The clamp keeps q on the triangle whatever the rounding of a sliver's region tests did, so the
+ *     function is total on finite input and never reports less than the true distance by more than a few
+ *     roundings.  For slivers q may be a point of the triangle that is not the closest one: the answer
+ *     below is DEFINED as the minimum of this function, not of the exact distance.
+ *   plane (normal as makePlane normalised it, point): s = normal . (p - point), q = p - normal * s, d2 = s * s.
+ *   sphere (centre, sqRadius): len = |p - c|, r = sqrt(sqRadius), d = |len - r|, d2 = d * d,
+ *     q = c + (p - c) * (r / len), or c + (r, 0, 0) where len == 0.
+ *
+ * Point i, with bound2 = dist[i] * dist[i] if dist[i] > 0, 0 otherwise (NaN included), +inf where dist is NULL:
+ *   candidates: BVH (accelerator 3) and Naive (1): every plane, sphere and triangle and every area light.
+ *               An accelerator id that builds nothing: the area lights only.  Point lights never.
+ *   accepted:   d2 < bound2 and not NaN.  A src triangle or plane pair leaves that primitive out (the
+ *               mapping and the "no source" rule of mrt_cast_rays_device; a sphere or light pair is
+ *               accepted and changes nothing, as there).
+ *   the answer: the accepted candidate least by d2; on bit-equal d2 by kind (plane, sphere, triangle,
+ *               light); within a kind by the lower INPUT index - so BVH and Naive agree bit for bit.
+ *   nothing accepted: kind 0, index -1, dist2 = bound2, point 0, 0, 0, bary 0, 0.
+ * tests[i] counts the distance-function evaluations made for point i: diagnostic, and the one output that
+ * may differ between accelerators and builds (under BVH a certified cull skips boxes that cannot hold a
+ * winner or a tie: DESIGN.md, "Nearest-point queries").
+ * RegularGrid (accelerator 2) is refused: -1 with a message, nothing done (no hierarchy to bound a
+ * distance with).  A device group is refused as for every query.
+ * Everything else as mrt_cast_rays_device: stream order and no host synchronisation; no allocation after
+ * a renderer's first query (deviceBytes grows by the mapping tables only); chunks of rayCap[0]; state
+ * (later frames, views and queries keep their bits and counts; the totals and frame statistics do not
+ * see the call); outSize as for mrt_cast_hits_device (fields beyond it count as NULL; fields are only
+ * ever appended).  Argument errors (a NULL handle, batch, point or out; n outside 1 .. 2^31 - 1; a stride
+ * of 1, 2 or below 0; outSize too small to hold kind; every field within outSize NULL) return -1 before
+ * any device work, with a message in mrt_last_error(); they are checked before the renderer is read. */
+typedef struct mrt_point_batch {
+    const float   *point;     /* device: point i's xyz at point + i * stride */
+    const float   *dist;      /* device or NULL: search radius per point; NULL = unbounded */
+    const int32_t *src;       /* device or NULL: n pairs (kind, input index) to leave out */
+    int64_t stride;           /* floats, >= 3; 0 means 3 */
+    int64_t n;                /* 1 .. 2^31 - 1 */
+} mrt_point_batch;
+typedef struct mrt_nearest {  /* packed device arrays or NULL (not wanted); fields only ever appended */
+    int32_t *kind, *index;    /* as mrt_cast_rays_device: 0 none, 1 plane .. 4 light; input order, -1 */
+    float   *dist2;           /* the squared distance, the function's own bits */
+    float   *point;           /* 3 */
+    float   *bary;            /* 2: u, v for a triangle or a light, else 0, 0 */
+    int32_t *tests;           /* primitives this point's distance function was evaluated on */
+} mrt_nearest;
+int mrt_nearest_points_device(mrt_renderer *r, const mrt_point_batch *pts, const mrt_nearest *out,
+                              size_t outSize, void *stream);
+/* host only, no GPU: the functions above on n (primitive, point) pairs.  kind 1: normal xyz, point xyz;
+ * 2: centre xyz, sqRadius; 3 (and 4): A, AB, AC.  points n x 3; dist2 n, nearest n x 3, bary n x 2, each
+ * may be NULL.  -1: a kind outside 1 .. 4, NULL prims or points, n < 0. */
+int mrt_point_distance(int32_t kind, const float *prims, const float *points, int64_t n,
+                       float *dist2, float *nearest, float *bary);
+/* test entry (needs a GPU): the same pairs through the device functions */
+int mrt_kat_point_distance(int32_t kind, const float *prims, const float *points, int32_t n,
+                           float *dist2, float *nearest, float *bary);
 
 /* ---- shaded ray queries (on the GPU; beyond the reference's entry points) ----
  * mrt_shade_rays_device: the radiance that arrives along each ray of a caller-supplied batch, as

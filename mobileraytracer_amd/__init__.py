@@ -454,6 +454,61 @@ class Renderer:
                                         **{"d_" + name: x.data_ptr() for name, x in out.items()})
         return out
 
+    # -- nearest-point queries -----------------------------------------------------------
+    NEAREST_FIELDS = tuple(name for name, _, _ in _native.NEAREST_FIELDS)
+
+    def nearest_points_device(self, d_point: int, n: int, /, *, d_dist: int = 0, d_src: int = 0, stride: int = 3,
+                              stream: int = 0, out_size: Optional[int] = None, **outputs: int) -> None:
+        """mrt_nearest_points_device: the nearest surface to each of ``n`` points resident in device
+        memory (point i's xyz at ``d_point`` + i * ``stride`` floats; both positional).  ``outputs``:
+        ``d_kind``, ``d_index``, ``d_dist2``, ``d_point`` (the nearest points), ``d_bary``, ``d_tests`` -
+        device pointers as ints to packed arrays (mrt_nearest), 0 or absent: not wanted.  ``d_dist``: the
+        search radius per point (n float32), 0: unbounded.  ``d_src``: (kind, input index) pairs to
+        leave out.  ``out_size``: the bytes of the structure the library may read (None: all of it).
+        ``stream`` as for cast_rays_device."""
+        out = _native.MrtNearest()
+        for key, value in outputs.items():
+            if not key.startswith("d_") or key[2:] not in self.NEAREST_FIELDS:
+                raise TypeError("nearest_points_device: unknown output %r" % key)
+            setattr(out, key[2:], value or None)
+        batch = _native.MrtPointBatch(d_point or None, d_dist or None, d_src or None, int(stride), int(n))
+        size = ctypes.sizeof(out) if out_size is None else int(out_size)
+        _native.check(self._lib.mrt_nearest_points_device(self._h, ctypes.byref(batch), ctypes.byref(out), size,
+                                                          ctypes.c_void_p(stream or None)))
+
+    def nearest_points(self, points, max_dist=None, src=None, fields=None):
+        """nearest_points_device for torch tensors on the renderer's device: ``points`` float32 (n, >= 3),
+        ``max_dist`` float32 (n,) or None (unbounded), ``src`` (n, 2) or None, with cast_rays' stream
+        joining.  Returns a dict of tensors, one per name in ``fields`` (None: all of
+        ``Renderer.NEAREST_FIELDS``): int32 ``kind`` / ``index`` / ``tests`` (n,), float32 ``dist2`` (n,),
+        ``point`` (n, 3) and ``bary`` (n, 2), allocated and ordered on torch's current stream.  An empty
+        batch returns empty tensors."""
+        import torch
+
+        device, n, points, stride, _, _ = self._ray_tensors(points, points)
+        fields = self.NEAREST_FIELDS if fields is None else tuple(fields)
+        if not fields or any(f not in self.NEAREST_FIELDS for f in fields):
+            raise ValueError("fields: at least one of %s" % (self.NEAREST_FIELDS,))
+        if max_dist is not None:
+            if max_dist.device != device or max_dist.shape != (n,):
+                raise ValueError("max_dist: a tensor of shape (%d,) on %s" % (n, device))
+            max_dist = max_dist.to(torch.float32).contiguous()
+        if src is not None:
+            if src.device != device or src.shape != (n, 2):
+                raise ValueError("src: a tensor of shape (%d, 2) on %s" % (n, device))
+            src = src.to(torch.int32).contiguous()
+        out = {}
+        for name, dtype, width in _native.NEAREST_FIELDS:
+            if name in fields:
+                out[name] = torch.empty(n if width == 1 else (n, width), dtype=getattr(torch, dtype), device=device)
+        if n == 0:
+            return out
+        with self._query_stream_of(device) as stream:
+            self.nearest_points_device(points.data_ptr(), n, d_dist=max_dist.data_ptr() if max_dist is not None else 0,
+                                       d_src=src.data_ptr() if src is not None else 0, stride=stride, stream=stream,
+                                       **{"d_" + name: x.data_ptr() for name, x in out.items()})
+        return out
+
     def first_hit_planes(self, camera=None, sample: int = 0, fields=None):
         """The first hit of every pixel's camera ray (sample ``sample``) as planes: camera_rays(camera,
         sample_base=sample, spp=1), then cast_hits, scattered by ``pixels`` into (height, width) or
@@ -776,6 +831,31 @@ def kat_triangle(tris, orig, dirs):
     hit, t = np.empty(len(tr), np.int32), np.empty(len(tr), np.float32)
     _native.check(_native.lib().mrt_kat_triangle(_ptr(tr), _ptr(o), _ptr(d), len(tr), _ptr(hit), _ptr(t)))
     return hit, t
+
+
+def _point_distance(fn, kind, prims, points):
+    kind = int(kind)
+    width = {1: 6, 2: 4, 3: 9, 4: 9}.get(kind, 9)
+    pr = np.ascontiguousarray(prims, np.float32).reshape(-1, width)
+    pt = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    if len(pr) != len(pt):
+        raise ValueError("point_distance: as many primitives as points")
+    d2 = np.empty(len(pt), np.float32)
+    q, uv = np.empty((len(pt), 3), np.float32), np.empty((len(pt), 2), np.float32)
+    _native.check(fn(kind, _ptr(pr), _ptr(pt), len(pt), _ptr(d2), _ptr(q), _ptr(uv)))
+    return d2, q, uv
+
+
+def point_distance(kind, prims, points):
+    """mrt_point_distance (host, no GPU): the nearest-point query's distance functions on (primitive,
+    point) pairs.  kind 1: plane (normal, point); 2: sphere (centre, sqRadius); 3 / 4: triangle / area
+    light (A, AB, AC).  Returns dist2 (n,), nearest (n, 3), bary (n, 2), float32."""
+    return _point_distance(_native.lib().mrt_point_distance, kind, prims, points)
+
+
+def kat_point_distance(kind, prims, points):
+    """The same pairs through the device's distance functions (needs a GPU)."""
+    return _point_distance(_native.lib().mrt_kat_point_distance, kind, prims, points)
 
 
 def kat_accumulate(rgb, spp, sample_base, bitmap, width, height, mode=0):

@@ -20,6 +20,7 @@
 #include "mrt_trace_ww.hpp"
 #include "mrt_trace_packet.hpp"
 #include "mrt_multi_hit.hpp"
+#include "mrt_nearest.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1609,6 +1610,73 @@ void launchMultiWalk(const DScene& s, const Level& lv, int* counters, int2* gsta
     else if (K <= 4) MRT_LAUNCH_MULTI(4);
     else MRT_LAUNCH_MULTI(kMultiHitsMax);
 #undef MRT_LAUNCH_MULTI
+}
+
+// ---------------------------------------------------------------------------------------
+// Nearest-point queries (mrt_nearest_points_device).  k_nearest_walk: k_multi_walk's frame - one point
+// per lane, a wave taking 64 points at a time from level 1's fetch cursor, the lane writing the caller's
+// arrays itself - around the best-first walk of mrt_nearest.hpp.  The stack is the keyed one (a child's
+// reference and its box distance, 8 B): 8 entries per lane in LDS, 4 KB per one-wave workgroup, deeper
+// entries in the closest-hit walk's spill area.  Nothing accepted: kind 0, index -1, dist2 = the bound,
+// point 0, 0, 0, bary 0, 0.
+__global__ __launch_bounds__(kNearestThreads) void k_nearest_walk(DScene s, Level lv, int* counters, int2* gstack,
+                                                                  int gdepth, QueryTables tb, const float* dist,
+                                                                  long long base, Nearest out) {
+    __shared__ int2 ldsStack[kLdsStackMin * kNearestThreads];
+    TStack st = makeKeyStack<kNearestThreads>(ldsStack, gstack, gdepth);
+    const SegMap map = segMap(counters, 1, false, lv.segCap);
+    int* fetch = counters + kCntFetchShards + 1 * kMaxFetchShards * kFetchStride;
+    while (true) {
+        int first = 0;
+        if (laneId() == 0) first = atomicAdd(fetch, 64);
+        first = __shfl(first, 0, 64);
+        if (first >= map.total()) break;
+        const int v = first + laneId();
+        if (v < map.total()) {
+            const int i = map.phys(v);
+            const long long g = base + i;  // the point's index in the caller's batch (k_query_load put it at i)
+            const float4 o4 = lv.rO[i];
+            const uint32_t src = fbits(lv.rD[i].w);
+            float bound2 = __builtin_inff();
+            if (dist != nullptr) {
+                const float d = dist[g];
+                bound2 = d > 0.0F ? d * d : 0.0F;  // (a NaN radius finds nothing)
+            }
+            const NearestBest nb = nearestPoint(s, tb, xyz(o4), bound2, src, st);
+            const bool held = nb.code != kNoPrim;
+            if (out.kind != nullptr) out.kind[g] = static_cast<int32_t>(primKind(nb.code));
+            if (out.index != nullptr) out.index[g] = held ? nearestInput(tb, nb.code) : -1;
+            if (out.dist2 != nullptr) out.dist2[g] = nb.d2;
+            store3(out.point, g, nb.q);
+            store2(out.bary, g, nb.u, nb.v);
+            if (out.tests != nullptr) out.tests[g] = nb.tests;
+        }
+    }
+}
+
+void launchNearestWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth, const QueryTables& tb,
+                       const float* dist, long long base, int n, const Nearest& out, int maxThreads, hipStream_t st) {
+    // a persistent grid over the fetch cursor: a wave per 64 points, at most the threads the spill area holds
+    const dim3 blocks(std::max(1, std::min(maxThreads / kNearestThreads, (n + kNearestThreads - 1) / kNearestThreads)));
+    hipLaunchKernelGGL(k_nearest_walk, blocks, dim3(kNearestThreads), 0, st, s, lv, counters, gstack, gdepth, tb, dist,
+                       base, out);
+}
+
+__global__ __launch_bounds__(64) void k_kat_point_distance(int kind, const float* prims, const float* points, int n,
+                                                           float* dist2, float* nearest, float* bary) {
+    const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const v3 p{points[3 * i], points[3 * i + 1], points[3 * i + 2]};
+    const PointDist r = pointPrim(kind, prims + static_cast<long long>(i) * pointPrimFloats(kind), p);
+    if (dist2 != nullptr) dist2[i] = r.d2;
+    store3(nearest, i, r.q);
+    store2(bary, i, r.u, r.v);
+}
+
+void launchKatPointDistance(int kind, const float* prims, const float* points, int n, float* dist2, float* nearest,
+                            float* bary, hipStream_t st) {
+    hipLaunchKernelGGL(k_kat_point_distance, dim3((n + 63) / 64), dim3(64), 0, st, kind, prims, points, n, dist2, nearest,
+                       bary);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -350,6 +350,26 @@ struct MultiHits {
 void launchMultiWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth, const QueryTables& tb,
                      const float* dist, long long base, int n, int K, const MultiHits& out, int maxThreads,
                      hipStream_t st);
+// Nearest-point queries (mrt_nearest_points_device): the device arrays of mrt_nearest, packed (point g's
+// kind at g, its nearest point at 3 g, its bary at 2 g) or null (not wanted: not stored).
+struct Nearest {
+    int32_t* kind;
+    int32_t* index;
+    float* dist2;
+    float* point;  // 3
+    float* bary;   // 2
+    int32_t* tests;
+};
+// k_nearest_walk (mrt_nearest.hpp): the n points k_query_load put into lv's queue (the origins; the
+// direction slots are not read, rD.w is the mapped source) answered by the walk and stored by it at
+// base + i, indices mapped to input order through tb.  dist: the caller's radius array (point base + i's
+// at dist[base + i]) or null (unbounded).  The spill area is the closest-hit walk's, as launchMultiWalk's.
+void launchNearestWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth, const QueryTables& tb,
+                       const float* dist, long long base, int n, const Nearest& out, int maxThreads, hipStream_t st);
+// known answers: pair i (kind's record at prims + i * pointPrimFloats(kind), point at points + 3 i)
+// through the device's distance functions
+void launchKatPointDistance(int kind, const float* prims, const float* points, int n, float* dist2, float* nearest,
+                            float* bary, hipStream_t st);
 // Shaded ray queries (mrt_shade_rays_device).  k_query_load's keyed form: n rays of q into lv's queue
 // as level-1 records of a frame's kind - rO.w the path key (keys[base + i]; null: pathKey(base + i, 0)),
 // rD.w the mapped source, tree = 1 - with the dense segment counts.

@@ -26,6 +26,7 @@
 #include "mobilert_amd.h"
 #include "mobilert_amd.hpp"
 #include "mrt_kernels.hpp"
+#include "mrt_nearest.hpp"
 #include "mrt_queue_plan.hpp"
 #include "mrt_scene.hpp"
 
@@ -2033,6 +2034,65 @@ void castMultiHits(mrt_renderer* r, mrt::QueryRays q, int64_t n, int K, const mr
     MRT_HIP(hipGetLastError());
 }
 
+// ---- nearest-point queries (mrt_nearest_points_device) -----------------------------------------
+// The argument checks, all before any device work, the batch and the outputs before the renderer is
+// read; fills the batch (the points as the query load's origins; its direction slots read the same
+// floats and are never used) and the outputs: the first outSize bytes of *out, whole fields only.
+mrt::QueryRays checkPointBatch(const mrt_renderer* r, const mrt_point_batch* pts, const mrt_nearest* out, size_t outSize,
+                               mrt::Nearest* nr) {
+    if (r == nullptr) throw std::runtime_error("mrt_nearest_points_device: null renderer");
+    if (pts == nullptr) throw std::runtime_error("mrt_nearest_points_device: null point batch");
+    if (pts->point == nullptr) throw std::runtime_error("mrt_nearest_points_device: null point");
+    if (out == nullptr) throw std::runtime_error("mrt_nearest_points_device: null outputs");
+    if (outSize < offsetof(mrt_nearest, kind) + sizeof(out->kind))
+        throw std::runtime_error("mrt_nearest_points_device: outSize too small to hold kind");
+    static_assert(sizeof(mrt_nearest) == 6 * sizeof(void*), "mrt_nearest: pointers only (fields are appended)");
+    mrt_nearest o{};
+    std::memcpy(&o, out, std::min(outSize, sizeof(o)) / sizeof(void*) * sizeof(void*));
+    *nr = mrt::Nearest{o.kind, o.index, o.dist2, o.point, o.bary, o.tests};
+    if (o.kind == nullptr && o.index == nullptr && o.dist2 == nullptr && o.point == nullptr && o.bary == nullptr &&
+        o.tests == nullptr)
+        throw std::runtime_error("mrt_nearest_points_device: no output (every field within outSize is null)");
+    if (pts->n < 1 || pts->n > 0x7fffffffLL) throw std::runtime_error("mrt_nearest_points_device: n must be 1 .. 2^31 - 1");
+    if (pts->stride != 0 && pts->stride < 3)
+        throw std::runtime_error("mrt_nearest_points_device: stride must be 0 (packed) or >= 3 floats");
+    mrt::QueryRays q{};
+    q.orig = pts->point;
+    q.dir = pts->point;
+    q.dist = pts->dist;
+    q.src = pts->src;
+    q.origStride = q.dirStride = pts->stride == 0 ? 3 : pts->stride;
+    if (!r->peers.empty()) throw std::runtime_error("mrt_nearest_points_device: device groups are not supported for queries");
+    if (r->ds.accel == mrt::kAccGrid)
+        throw std::runtime_error("mrt_nearest_points_device: the RegularGrid accelerator (2) is not supported: the grid "
+                                 "has no hierarchy to bound a distance with");
+    return q;
+}
+
+// castMultiHits' chunk loop with the nearest-point walk: the points go into level 1's queue as a
+// closest-hit query's origins (k_query_load maps the sources), k_nearest_walk writes the caller's arrays.
+void nearestPoints(mrt_renderer* r, mrt::QueryRays q, int64_t n, const mrt::Nearest& out) {
+    using namespace mrt;
+    hipStream_t st = r->stream;
+    const QueryTables& tb = queryTables(r);
+    mrt_renderer::Pipe& pp = r->pipe;
+    const Level& lv = pp.levels[1];  // (the plan in use now, as castRays)
+    const int64_t cap = std::min<int64_t>(lv.cap, static_cast<int64_t>(kQueueSegs) * lv.segCap);
+    if (cap <= 0) throw std::runtime_error("mrt_nearest_points_device: the level-1 queue holds no rays");
+    const int walkThreads = r->walkGridCap > 0 ? std::min(r->traceThreads, r->walkGridCap * kBlock) : r->traceThreads;
+    const float* dist = q.dist;
+    q.dist = nullptr;  // (the load is the closest-hit form's: it reads no dist)
+    for (int64_t base = 0; base < n; base += cap) {
+        const int m = static_cast<int>(std::min<int64_t>(cap, n - base));
+        q.base = base;
+        MRT_HIP(hipMemsetAsync(pp.counters, 0, sizeof(int) * kNumCounters, st));
+        r->countersClean = false;  // (left in use: the next pass resets them)
+        launchQueryLoad(lv, q, tb, m, false, pp.counters, st);
+        launchNearestWalk(r->ds, lv, pp.counters, pp.gstack, r->gdepth, tb, dist, base, m, out, walkThreads, st);
+    }
+    MRT_HIP(hipGetLastError());
+}
+
 // ---- shaded ray queries (mrt_shade_rays_device) ------------------------------------------------
 // The argument checks, all before any device work, in checkRayBatch's order: the batch and the
 // output first (those checks do not read the renderer).
@@ -2331,6 +2391,26 @@ int mrt_cast_multi_hits_device(mrt_renderer* r, const mrt_ray_batch* rays, int32
             MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
         }
         castMultiHits(r, q, rays->n, K, mh);
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinOut, r->stream));
+            MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
+        }
+    });
+}
+
+int mrt_nearest_points_device(mrt_renderer* r, const mrt_point_batch* pts, const mrt_nearest* out, size_t outSize,
+                              void* stream) {
+    return guarded([&] {
+        mrt::Nearest nr{};
+        const mrt::QueryRays q = checkPointBatch(r, pts, out, outSize, &nr);
+        MRT_HIP(hipSetDevice(r->device));
+        hipStream_t st = stream != nullptr ? static_cast<hipStream_t>(stream) : r->stream;
+        // joined to the caller's stream on both sides, as mrt_cast_rays_device
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinIn, st));
+            MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
+        }
+        nearestPoints(r, q, pts->n, nr);
         if (st != r->stream) {
             MRT_HIP(hipEventRecord(r->joinOut, r->stream));
             MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
@@ -3068,6 +3148,50 @@ int mrt_kat_triangle(const float* tris, const float* orig, const float* dir, int
         mrt::launchKatTriangle(b.as<float>(), o.as<float>(), d.as<float>(), n, h.as<int32_t>(), tt.as<float>(), nullptr);
         MRT_HIP(hipMemcpy(hit, h.p, N * 4, hipMemcpyDeviceToHost));
         MRT_HIP(hipMemcpy(t, tt.p, N * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+// the argument checks of mrt_point_distance and its device twin
+static void checkPointPairs(const char* who, int32_t kind, const float* prims, const float* points, int64_t n) {
+    if (kind < 1 || kind > 4) throw std::runtime_error(std::string(who) + ": kind must be 1 plane, 2 sphere, 3 triangle or 4 light");
+    if (prims == nullptr || points == nullptr) throw std::runtime_error(std::string(who) + ": null prims / points");
+    if (n < 0) throw std::runtime_error(std::string(who) + ": n must be >= 0");
+}
+
+int mrt_point_distance(int32_t kind, const float* prims, const float* points, int64_t n, float* dist2, float* nearest,
+                       float* bary) {
+    return guarded([&] {
+        checkPointPairs("mrt_point_distance", kind, prims, points, n);
+        const int w = mrt::pointPrimFloats(kind);
+        for (int64_t i = 0; i < n; ++i) {
+            const mrt::v3 p{points[3 * i], points[3 * i + 1], points[3 * i + 2]};
+            const mrt::PointDist d = mrt::pointPrim(kind, prims + i * w, p);
+            if (dist2 != nullptr) dist2[i] = d.d2;
+            if (nearest != nullptr) put3(nearest + 3 * i, d.q);
+            if (bary != nullptr) {
+                bary[2 * i] = d.u;
+                bary[2 * i + 1] = d.v;
+            }
+        }
+    });
+}
+
+int mrt_kat_point_distance(int32_t kind, const float* prims, const float* points, int32_t n, float* dist2,
+                           float* nearest, float* bary) {
+    return guarded([&] {
+        checkPointPairs("mrt_kat_point_distance", kind, prims, points, n);
+        if (n == 0) return;
+        const size_t N = static_cast<size_t>(n), w = static_cast<size_t>(mrt::pointPrimFloats(kind));
+        DevBuf b(N * w * 4), p(N * 12), d(N * 4), q(N * 12), uv(N * 8);
+        MRT_HIP(hipMemcpy(b.p, prims, N * w * 4, hipMemcpyHostToDevice));
+        MRT_HIP(hipMemcpy(p.p, points, N * 12, hipMemcpyHostToDevice));
+        mrt::launchKatPointDistance(kind, b.as<float>(), p.as<float>(), n, d.as<float>(), q.as<float>(), uv.as<float>(),
+                                    nullptr);
+        MRT_HIP(hipGetLastError());
+        if (dist2 != nullptr) MRT_HIP(hipMemcpy(dist2, d.p, N * 4, hipMemcpyDeviceToHost));
+        if (nearest != nullptr) MRT_HIP(hipMemcpy(nearest, q.p, N * 12, hipMemcpyDeviceToHost));
+        if (bary != nullptr) MRT_HIP(hipMemcpy(bary, uv.p, N * 8, hipMemcpyDeviceToHost));
+        MRT_HIP(hipDeviceSynchronize());
     });
 }
 
