@@ -28,6 +28,8 @@
  *                             the nearest surface to each of the caller's points: which primitive, the squared
  *                             distance, the point on it and its barycentrics (no reference call: the reference
  *                             answers questions about rays only); mrt_point_distance is its definition on the host
+ *   mrt_neighbours_device     the K nearest surfaces to each of the caller's points, in order, and the number
+ *                             within the point's radius (no reference call)
  *   mrt_scene_triangles / _planes / _spheres / _materials / _lights
  *                             Shader::getTriangles / getPlanes / getSpheres / getMaterials / getLights
  *                             (Shader.hpp:92-100) in the scene's input order
@@ -655,6 +657,60 @@ int mrt_point_distance(int32_t kind, const float *prims, const float *points, in
 /* test entry (needs a GPU): the same pairs through the device functions */
 int mrt_kat_point_distance(int32_t kind, const float *prims, const float *points, int32_t n,
                            float *dist2, float *nearest, float *bary);
+
+/* ---- neighbour queries (on the GPU; beyond the reference's entry points) ----
+ * mrt_neighbours_device: for each point of a caller-supplied batch the K nearest surfaces of the loaded
+ * scene, in order, and the number of surfaces within the point's radius: contact generation (every
+ * surface within a margin), snapping and distance fields blended over the few nearest faces, local
+ * density - in one walk instead of re-queries with src exclusions.  It is to mrt_nearest_points_device
+ * what mrt_cast_multi_hits_device is to mrt_cast_rays_device.
+ *
+ * The batch is mrt_point_batch.  Candidates, acceptance, bound2 and sources are exactly those of
+ * mrt_nearest_points_device: BVH (3) and Naive (1): every plane, sphere, triangle and area light; an
+ * accelerator id that builds nothing: the area lights only; point lights never.  A candidate is accepted
+ * when d2 < bound2 and d2 is not NaN, with bound2 = dist[i] * dist[i] if dist[i] > 0, 0 otherwise (NaN
+ * included), +inf where dist is NULL.  A src triangle or plane pair leaves that primitive out; a sphere or
+ * light pair is accepted and changes nothing; a pair whose kind is not 1 .. 4 or whose index is out of
+ * range carries no source.
+ * count[i] is the number of accepted candidates, not capped by K.
+ * The list is the first min(count, K) accepted candidates in the nearest-point query's total order: by
+ * d2; on bit-equal d2 by kind (plane, sphere, triangle, light); within a kind by the lower INPUT index.
+ * Entry 0 is therefore mrt_nearest_points_device's answer, bit for bit, in every field, and BVH and Naive
+ * agree bit for bit in every field but tests.  dist2, point and bary of an entry are the bits
+ * mrt_point_distance gives for that (primitive, point) pair.
+ * Entries count .. K - 1 are padding: kind 0, index -1, dist2 = bound2, point 0, 0, 0, bary 0, 0.
+ *
+ * What the walk may skip, and so what a call costs.  Under BVH a box is skipped only on the certified
+ * bound of the nearest-point walk: lb > thr, thr = (sqrt(b) + 2 c1)^2 (1 + 2^-20) with the lemma's k = 32,
+ * the compare strict and false for NaN ("Neighbour queries").  What b is depends on the outputs:
+ *   count wanted:      b = bound2 and never shrinks: every accepted candidate must be met, whether or
+ *                      not it enters the list.  With dist NULL this walks every primitive; that is
+ *                      allowed, and costs what Naive costs.
+ *   count not wanted:  b = min(bound2, the list's K-th d2 once the list is full), recomputed when that
+ *                      changes: the K-nearest search.  A candidate bit-equal to the K-th entry and
+ *                      earlier in the order still displaces it (its box is never skipped).
+ * tests[i] counts the distance-function evaluations made for point i (diagnostic; it differs between
+ * accelerators and between the two forms).
+ * RegularGrid (accelerator 2) and device groups are refused as for every point query: -1 with a message,
+ * nothing done.  Everything else as mrt_nearest_points_device: stream order and no host synchronisation;
+ * no allocation after a renderer's first query (the walk writes the caller's arrays itself); chunks of
+ * rayCap[0]; state (later frames, views and queries keep their bits and counts; the totals and frame
+ * statistics do not see the call); outSize (fields beyond it count as NULL; fields are only ever
+ * appended).  Argument errors (a NULL handle, batch, point or out; K outside 1 .. MRT_NEIGHBOURS_MAX; n
+ * outside 1 .. 2^31 - 1; a stride of 1, 2 or below 0; outSize too small to hold count; every field within
+ * outSize NULL) return -1 before any device work, with a message in mrt_last_error(); they are checked
+ * before the renderer is read. */
+#define MRT_NEIGHBOURS_MAX 16
+typedef struct mrt_neighbours {   /* packed device arrays or NULL (not wanted); fields only ever appended */
+    int32_t *count;               /* n: the size of point i's accepted set, not capped by K */
+    int32_t *kind, *index;        /* n x K, entry k of point i at i * K + k; values as mrt_nearest */
+    float   *dist2;               /* n x K */
+    float   *point;               /* n x K x 3 */
+    float   *bary;                /* n x K x 2 */
+    int32_t *tests;               /* n: distance-function evaluations made for point i (diagnostic) */
+} mrt_neighbours;
+int mrt_neighbours_device(mrt_renderer *r, const mrt_point_batch *pts, int32_t K,
+                          const mrt_neighbours *out, size_t outSize, void *stream);
 
 /* ---- shaded ray queries (on the GPU; beyond the reference's entry points) ----
  * mrt_shade_rays_device: the radiance that arrives along each ray of a caller-supplied batch, as

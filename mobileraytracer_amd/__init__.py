@@ -509,6 +509,65 @@ class Renderer:
                                        **{"d_" + name: x.data_ptr() for name, x in out.items()})
         return out
 
+    # -- neighbour queries ---------------------------------------------------------------
+    NEIGHBOUR_FIELDS = tuple(name for name, _, _ in _native.NEIGHBOUR_FIELDS)
+
+    def neighbours_device(self, d_point: int, n: int, k: int, /, *, d_dist: int = 0, d_src: int = 0, stride: int = 3,
+                          stream: int = 0, out_size: Optional[int] = None, **outputs: int) -> None:
+        """mrt_neighbours_device: the ``k`` (1 .. 16) nearest surfaces to each of ``n`` points resident in
+        device memory, in order, and the number within each point's radius.  ``outputs``: ``d_count`` and
+        ``d_tests`` (n int32), ``d_kind`` / ``d_index`` (n x k int32), ``d_dist2`` (n x k float32),
+        ``d_point`` (n x k x 3), ``d_bary`` (n x k x 2) - device pointers as ints to packed arrays
+        (mrt_neighbours), 0 or absent: not wanted.  With ``d_count`` the walk meets every surface within
+        the radius (``d_dist``; 0: unbounded, every primitive); without it, it is the K-nearest search.
+        Points, ``d_dist``, ``d_src``, ``stride``, ``out_size`` and ``stream`` as for nearest_points_device."""
+        out = _native.MrtNeighbours()
+        for key, value in outputs.items():
+            if not key.startswith("d_") or key[2:] not in self.NEIGHBOUR_FIELDS:
+                raise TypeError("neighbours_device: unknown output %r" % key)
+            setattr(out, key[2:], value or None)
+        batch = _native.MrtPointBatch(d_point or None, d_dist or None, d_src or None, int(stride), int(n))
+        size = ctypes.sizeof(out) if out_size is None else int(out_size)
+        _native.check(self._lib.mrt_neighbours_device(self._h, ctypes.byref(batch), int(k), ctypes.byref(out), size,
+                                                      ctypes.c_void_p(stream or None)))
+
+    def neighbours(self, points, k: int, max_dist=None, src=None, fields=None):
+        """neighbours_device for torch tensors on the renderer's device, with nearest_points' handling of
+        ``points`` / ``max_dist`` / ``src`` and its stream joining.  Returns a dict of tensors, one per
+        name in ``fields`` (None: all of ``Renderer.NEIGHBOUR_FIELDS``): int32 ``count`` / ``tests`` (n,),
+        int32 ``kind`` / ``index`` (n, k), float32 ``dist2`` (n, k), ``point`` (n, k, 3) and ``bary``
+        (n, k, 2), allocated and ordered on torch's current stream.  Leaving ``count`` out of ``fields``
+        makes the walk the K-nearest search.  An empty batch returns empty tensors."""
+        import torch
+
+        device, n, points, stride, _, _ = self._ray_tensors(points, points)
+        k = int(k)
+        if not 1 <= k <= _native.NEIGHBOURS_MAX:
+            raise ValueError("k: 1 .. %d" % _native.NEIGHBOURS_MAX)
+        fields = self.NEIGHBOUR_FIELDS if fields is None else tuple(fields)
+        if not fields or any(f not in self.NEIGHBOUR_FIELDS for f in fields):
+            raise ValueError("fields: at least one of %s" % (self.NEIGHBOUR_FIELDS,))
+        if max_dist is not None:
+            if max_dist.device != device or max_dist.shape != (n,):
+                raise ValueError("max_dist: a tensor of shape (%d,) on %s" % (n, device))
+            max_dist = max_dist.to(torch.float32).contiguous()
+        if src is not None:
+            if src.device != device or src.shape != (n, 2):
+                raise ValueError("src: a tensor of shape (%d, 2) on %s" % (n, device))
+            src = src.to(torch.int32).contiguous()
+        out = {}
+        for name, dtype, width in _native.NEIGHBOUR_FIELDS:
+            if name in fields:
+                shape = (n,) if width == 0 else (n, k) if width == 1 else (n, k, width)
+                out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=device)
+        if n == 0:
+            return out
+        with self._query_stream_of(device) as stream:
+            self.neighbours_device(points.data_ptr(), n, k, d_dist=max_dist.data_ptr() if max_dist is not None else 0,
+                                   d_src=src.data_ptr() if src is not None else 0, stride=stride, stream=stream,
+                                   **{"d_" + name: x.data_ptr() for name, x in out.items()})
+        return out
+
     def first_hit_planes(self, camera=None, sample: int = 0, fields=None):
         """The first hit of every pixel's camera ray (sample ``sample``) as planes: camera_rays(camera,
         sample_base=sample, spp=1), then cast_hits, scattered by ``pixels`` into (height, width) or

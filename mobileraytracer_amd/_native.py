@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "mrt_path_key", "mrt_shade_rays_device", "mrt_camera_rays_device",
     "mrt_cast_hits_device", "mrt_cast_multi_hits_device", "mrt_scene_triangles", "mrt_scene_planes", "mrt_scene_spheres", "mrt_scene_materials",
     "mrt_scene_lights", "mrt_nearest_points_device", "mrt_point_distance", "mrt_kat_point_distance",
+    "mrt_neighbours_device",
     "RayTrace", "stopRender",
 )
 
@@ -100,6 +101,17 @@ NEAREST_FIELDS = (("kind", "int32", 1), ("index", "int32", 1), ("dist2", "float3
 
 class MrtNearest(ctypes.Structure):  # mrt_nearest: device arrays of a nearest-point query, NULL = not wanted
     _fields_ = [(name, ctypes.c_void_p) for name, _, _ in NEAREST_FIELDS]
+
+
+NEIGHBOURS_MAX = 16  # MRT_NEIGHBOURS_MAX
+# mrt_neighbours: the fields in the header's order, (name, dtype, entries per point: 0 = one per point, else
+# floats or ints per list entry)
+NEIGHBOUR_FIELDS = (("count", "int32", 0), ("kind", "int32", 1), ("index", "int32", 1), ("dist2", "float32", 1),
+                    ("point", "float32", 3), ("bary", "float32", 2), ("tests", "int32", 0))
+
+
+class MrtNeighbours(ctypes.Structure):  # mrt_neighbours: device arrays of a neighbour query, NULL = not wanted
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in NEIGHBOUR_FIELDS]
 
 
 class MrtShadeBatch(ctypes.Structure):  # mrt_shade_batch: rays and their path keys (mrt_shade_rays_device)
@@ -248,6 +260,8 @@ def load_library(path=LIB_PATH):
         "mrt_cast_multi_hits_device": (ctypes.c_int, [vp, P(MrtRayBatch), ctypes.c_int32, P(MrtMultiHits),
                                                       ctypes.c_size_t, vp]),
         "mrt_nearest_points_device": (ctypes.c_int, [vp, P(MrtPointBatch), P(MrtNearest), ctypes.c_size_t, vp]),
+        "mrt_neighbours_device": (ctypes.c_int, [vp, P(MrtPointBatch), ctypes.c_int32, P(MrtNeighbours),
+                                                 ctypes.c_size_t, vp]),
         "mrt_point_distance": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int64, vp, vp, vp]),
         "mrt_kat_point_distance": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int32, vp, vp, vp]),
         "mrt_scene_triangles": (ctypes.c_int64, [vp, vp, vp, vp, vp]),
@@ -285,7 +299,7 @@ def source_stamp():
     srcs = ["mrt_scene.cpp", "mrt_grid.cpp", "mrt_texture.cpp", "mrt_android.cpp", "mrt_queue_plan.cpp", "mrt_kernels.hip",
             "mrt_renderer.hip",
             "mrt_common.hpp", "mrt_device.hpp", "mrt_kernels.hpp", "mrt_trace_ww.hpp", "mrt_trace_packet.hpp",
-            "mrt_multi_hit.hpp", "mrt_nearest.hpp", "mrt_scene.hpp", "mrt_queue_plan.hpp", "../../include/mobilert_amd.h", "../../include/mobilert_amd.hpp",
+            "mrt_multi_hit.hpp", "mrt_nearest.hpp", "mrt_neighbours.hpp", "mrt_scene.hpp", "mrt_queue_plan.hpp", "../../include/mobilert_amd.h", "../../include/mobilert_amd.hpp",
             "../../include/mobilert_android.h"]
     h = hashlib.sha256()
     for f in srcs:

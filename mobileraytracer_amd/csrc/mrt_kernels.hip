@@ -21,6 +21,7 @@
 #include "mrt_trace_packet.hpp"
 #include "mrt_multi_hit.hpp"
 #include "mrt_nearest.hpp"
+#include "mrt_neighbours.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1660,6 +1661,84 @@ void launchNearestWalk(const DScene& s, const Level& lv, int* counters, int2* gs
     const dim3 blocks(std::max(1, std::min(maxThreads / kNearestThreads, (n + kNearestThreads - 1) / kNearestThreads)));
     hipLaunchKernelGGL(k_nearest_walk, blocks, dim3(kNearestThreads), 0, st, s, lv, counters, gstack, gdepth, tb, dist,
                        base, out);
+}
+
+// ---------------------------------------------------------------------------------------
+// Neighbour queries (mrt_neighbours_device).  k_neighbour_walk: k_nearest_walk's frame around the list
+// walk of mrt_neighbours.hpp.  kCeil: the list's size in LDS (1, 4 or 16 entries of 8 B per lane) - with
+// the 4 KB of stack 4.5, 6 and 12 KB per one-wave workgroup.  kCount: the count is wanted, so the walk's
+// bound stays the point's radius; false is the K-nearest search, whose bound is the list's K-th entry.
+// The wave's 64 points are adjacent, so count and tests are coalesced stores and entry k of a field a
+// store of stride K records; entries count .. K - 1 are written as padding (kind 0, index -1, dist2 =
+// bound2, point 0, 0, 0, bary 0, 0).  point and bary come from evaluating the held entries' distance
+// functions once more (neighbourEval), and only where one of them is wanted.
+template <int kCeil, bool kCount>
+__global__ __launch_bounds__(kNeighbourThreads) void k_neighbour_walk(DScene s, Level lv, int* counters, int2* gstack,
+                                                                      int gdepth, QueryTables tb, const float* dist,
+                                                                      long long base, int K, Neighbours out) {
+    __shared__ int2 ldsStack[kLdsStackMin * kNeighbourThreads];
+    __shared__ float nlD2[kCeil * kNeighbourThreads];
+    __shared__ uint32_t nlCode[kCeil * kNeighbourThreads];
+    TStack st = makeKeyStack<kNeighbourThreads>(ldsStack, gstack, gdepth);
+    NeighbourList<kCount> nl{nlD2 + threadIdx.x, nlCode + threadIdx.x, min(K, kCeil), 0, 0, 0, 0.0F, 0.0F, 0.0F, 0.0F};
+    const SegMap map = segMap(counters, 1, false, lv.segCap);
+    int* fetch = counters + kCntFetchShards + 1 * kMaxFetchShards * kFetchStride;
+    const bool wantQ = out.point != nullptr || out.bary != nullptr;
+    while (true) {
+        int first = 0;
+        if (laneId() == 0) first = atomicAdd(fetch, 64);
+        first = __shfl(first, 0, 64);
+        if (first >= map.total()) break;
+        const int v = first + laneId();
+        if (v < map.total()) {
+            const int i = map.phys(v);
+            const long long g = base + i;  // the point's index in the caller's batch (k_query_load put it at i)
+            const v3 p = xyz(lv.rO[i]);
+            const uint32_t src = fbits(lv.rD[i].w);
+            float bound2 = __builtin_inff();
+            if (dist != nullptr) {
+                const float d = dist[g];
+                bound2 = d > 0.0F ? d * d : 0.0F;  // (a NaN radius finds nothing)
+            }
+            nl.reset(bound2);
+            neighbourPoint(s, tb, p, src, nl, st);
+            if (kCount) out.count[g] = nl.count;
+            if (out.tests != nullptr) out.tests[g] = nl.tests;
+            const long long e0 = g * K;
+            for (int k = 0; k < nl.K; ++k) {
+                const bool held = k < nl.n;
+                const uint32_t code = held ? nl.code[k * kNeighbourThreads] : kNoPrim;
+                if (out.kind != nullptr) out.kind[e0 + k] = static_cast<int32_t>(primKind(code));
+                if (out.index != nullptr) out.index[e0 + k] = held ? nearestInput(tb, code) : -1;
+                if (out.dist2 != nullptr) out.dist2[e0 + k] = held ? nl.d2[k * kNeighbourThreads] : bound2;
+                if (wantQ) {
+                    const PointDist r = neighbourEval(s, code, p);  // (kNoPrim: zeros)
+                    store3(out.point, e0 + k, r.q);
+                    store2(out.bary, e0 + k, r.u, r.v);
+                }
+            }
+        }
+    }
+}
+
+void launchNeighbourWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth, const QueryTables& tb,
+                         const float* dist, long long base, int n, int K, const Neighbours& out, int maxThreads,
+                         hipStream_t st) {
+    // a persistent grid over the fetch cursor: a wave per 64 points, at most the threads the spill area holds
+    const dim3 blocks(std::max(1, std::min(maxThreads / kNeighbourThreads, (n + kNeighbourThreads - 1) / kNeighbourThreads)));
+#define MRT_LAUNCH_NEIGHBOUR(CEIL, COUNT) \
+    hipLaunchKernelGGL((k_neighbour_walk<CEIL, COUNT>), blocks, dim3(kNeighbourThreads), 0, st, s, lv, counters, gstack, gdepth, tb, dist, base, K, out)
+#define MRT_LAUNCH_NEIGHBOUR_K(COUNT)                \
+    if (K <= 1) MRT_LAUNCH_NEIGHBOUR(1, COUNT);      \
+    else if (K <= 4) MRT_LAUNCH_NEIGHBOUR(4, COUNT); \
+    else MRT_LAUNCH_NEIGHBOUR(kNeighboursMax, COUNT)
+    if (out.count != nullptr) {
+        MRT_LAUNCH_NEIGHBOUR_K(true);
+    } else {
+        MRT_LAUNCH_NEIGHBOUR_K(false);
+    }
+#undef MRT_LAUNCH_NEIGHBOUR_K
+#undef MRT_LAUNCH_NEIGHBOUR
 }
 
 __global__ __launch_bounds__(64) void k_kat_point_distance(int kind, const float* prims, const float* points, int n,

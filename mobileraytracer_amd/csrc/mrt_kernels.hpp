@@ -366,6 +366,26 @@ struct Nearest {
 // at dist[base + i]) or null (unbounded).  The spill area is the closest-hit walk's, as launchMultiWalk's.
 void launchNearestWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth, const QueryTables& tb,
                        const float* dist, long long base, int n, const Nearest& out, int maxThreads, hipStream_t st);
+// Neighbour queries (mrt_neighbours_device): the device arrays of mrt_neighbours, packed (point g's count
+// and tests at g, its entry k at g * K + k, three floats per entry of point, two of bary) or null (not
+// wanted: not stored).
+constexpr int kNeighboursMax = 16;  // MRT_NEIGHBOURS_MAX: the largest list
+struct Neighbours {
+    int32_t* count;
+    int32_t* kind;
+    int32_t* index;
+    float* dist2;
+    float* point;  // 3
+    float* bary;   // 2
+    int32_t* tests;
+};
+// k_neighbour_walk (mrt_neighbours.hpp): the n points k_query_load put into lv's queue, as
+// launchNearestWalk's, each point's first K accepted candidates (K 1 .. 16) in order, its count and the
+// padding stored by the walk itself at base + i.  Where out.count is null the walk is the K-nearest search
+// (its bound shrinks to the list's K-th entry); where it is wanted the bound stays the point's radius.
+void launchNeighbourWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth, const QueryTables& tb,
+                         const float* dist, long long base, int n, int K, const Neighbours& out, int maxThreads,
+                         hipStream_t st);
 // known answers: pair i (kind's record at prims + i * pointPrimFloats(kind), point at points + 3 i)
 // through the device's distance functions
 void launchKatPointDistance(int kind, const float* prims, const float* points, int n, float* dist2, float* nearest,

@@ -199,10 +199,12 @@ __device__ __forceinline__ float absMaxNan(float m, float x) {
     return (a > m || a != a) ? a : m;
 }
 
-// The reference tree, best first.  Stack: TStack (reference and box distance per entry).
-template <class Stack>
+// The reference tree, best first.  Stack: TStack (reference and box distance per entry).  Held: what the
+// lane keeps (NearestBest, or mrt_neighbours.hpp's list) - its c2, thr and setThr(), and a nearestTriangle
+// that offers it one triangle.
+template <class Stack, class Held>
 __device__ __forceinline__ void nearestTriangles(const DScene& s, const QueryTables& tb, v3 p, uint32_t src,
-                                                 NearestBest& nb, Stack& st) {
+                                                 Held& nb, Stack& st) {
     const GRoot& root = s.triRootRef;
     if (root.count == 0) return;
     float m = fabsf(p.x);

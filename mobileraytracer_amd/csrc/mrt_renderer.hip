@@ -2069,16 +2069,18 @@ mrt::QueryRays checkPointBatch(const mrt_renderer* r, const mrt_point_batch* pts
     return q;
 }
 
-// castMultiHits' chunk loop with the nearest-point walk: the points go into level 1's queue as a
-// closest-hit query's origins (k_query_load maps the sources), k_nearest_walk writes the caller's arrays.
-void nearestPoints(mrt_renderer* r, mrt::QueryRays q, int64_t n, const mrt::Nearest& out) {
+// castMultiHits' chunk loop for the point queries: the points go into level 1's queue as a closest-hit
+// query's origins (k_query_load maps the sources), and walk(lv, tb, dist, base, m, walkThreads, st) - the
+// nearest-point or the neighbour walk - writes the caller's arrays.
+template <class Walk>
+void pointChunks(mrt_renderer* r, mrt::QueryRays q, int64_t n, const char* name, Walk walk) {
     using namespace mrt;
     hipStream_t st = r->stream;
     const QueryTables& tb = queryTables(r);
     mrt_renderer::Pipe& pp = r->pipe;
     const Level& lv = pp.levels[1];  // (the plan in use now, as castRays)
     const int64_t cap = std::min<int64_t>(lv.cap, static_cast<int64_t>(kQueueSegs) * lv.segCap);
-    if (cap <= 0) throw std::runtime_error("mrt_nearest_points_device: the level-1 queue holds no rays");
+    if (cap <= 0) throw std::runtime_error(std::string(name) + ": the level-1 queue holds no rays");
     const int walkThreads = r->walkGridCap > 0 ? std::min(r->traceThreads, r->walkGridCap * kBlock) : r->traceThreads;
     const float* dist = q.dist;
     q.dist = nullptr;  // (the load is the closest-hit form's: it reads no dist)
@@ -2088,9 +2090,63 @@ void nearestPoints(mrt_renderer* r, mrt::QueryRays q, int64_t n, const mrt::Near
         MRT_HIP(hipMemsetAsync(pp.counters, 0, sizeof(int) * kNumCounters, st));
         r->countersClean = false;  // (left in use: the next pass resets them)
         launchQueryLoad(lv, q, tb, m, false, pp.counters, st);
-        launchNearestWalk(r->ds, lv, pp.counters, pp.gstack, r->gdepth, tb, dist, base, m, out, walkThreads, st);
+        walk(lv, tb, dist, base, m, walkThreads, st);
     }
     MRT_HIP(hipGetLastError());
+}
+
+void nearestPoints(mrt_renderer* r, mrt::QueryRays q, int64_t n, const mrt::Nearest& out) {
+    pointChunks(r, q, n, "mrt_nearest_points_device",
+                [&](const mrt::Level& lv, const mrt::QueryTables& tb, const float* dist, int64_t base, int m, int threads,
+                    hipStream_t st) {
+                    mrt::launchNearestWalk(r->ds, lv, r->pipe.counters, r->pipe.gstack, r->gdepth, tb, dist, base, m, out,
+                                           threads, st);
+                });
+}
+
+// ---- neighbour queries (mrt_neighbours_device) -------------------------------------------------
+// The argument checks, as checkPointBatch's: the batch, K and the outputs before the renderer is read.
+mrt::QueryRays checkNeighbourBatch(const mrt_renderer* r, const mrt_point_batch* pts, int32_t K, const mrt_neighbours* out,
+                                   size_t outSize, mrt::Neighbours* nb) {
+    if (r == nullptr) throw std::runtime_error("mrt_neighbours_device: null renderer");
+    if (pts == nullptr) throw std::runtime_error("mrt_neighbours_device: null point batch");
+    if (pts->point == nullptr) throw std::runtime_error("mrt_neighbours_device: null point");
+    if (out == nullptr) throw std::runtime_error("mrt_neighbours_device: null outputs");
+    if (K < 1 || K > MRT_NEIGHBOURS_MAX)
+        throw std::runtime_error("mrt_neighbours_device: K must be 1 .. " + std::to_string(MRT_NEIGHBOURS_MAX));
+    static_assert(MRT_NEIGHBOURS_MAX == mrt::kNeighboursMax, "the list's largest instantiation holds the header's K");
+    if (outSize < offsetof(mrt_neighbours, count) + sizeof(out->count))
+        throw std::runtime_error("mrt_neighbours_device: outSize too small to hold count");
+    static_assert(sizeof(mrt_neighbours) == 7 * sizeof(void*), "mrt_neighbours: pointers only (fields are appended)");
+    mrt_neighbours o{};
+    std::memcpy(&o, out, std::min(outSize, sizeof(o)) / sizeof(void*) * sizeof(void*));
+    *nb = mrt::Neighbours{o.count, o.kind, o.index, o.dist2, o.point, o.bary, o.tests};
+    if (o.count == nullptr && o.kind == nullptr && o.index == nullptr && o.dist2 == nullptr && o.point == nullptr &&
+        o.bary == nullptr && o.tests == nullptr)
+        throw std::runtime_error("mrt_neighbours_device: no output (every field within outSize is null)");
+    if (pts->n < 1 || pts->n > 0x7fffffffLL) throw std::runtime_error("mrt_neighbours_device: n must be 1 .. 2^31 - 1");
+    if (pts->stride != 0 && pts->stride < 3)
+        throw std::runtime_error("mrt_neighbours_device: stride must be 0 (packed) or >= 3 floats");
+    mrt::QueryRays q{};
+    q.orig = pts->point;
+    q.dir = pts->point;
+    q.dist = pts->dist;
+    q.src = pts->src;
+    q.origStride = q.dirStride = pts->stride == 0 ? 3 : pts->stride;
+    if (!r->peers.empty()) throw std::runtime_error("mrt_neighbours_device: device groups are not supported for queries");
+    if (r->ds.accel == mrt::kAccGrid)
+        throw std::runtime_error("mrt_neighbours_device: the RegularGrid accelerator (2) is not supported: the grid "
+                                 "has no hierarchy to bound a distance with");
+    return q;
+}
+
+void neighbourPoints(mrt_renderer* r, mrt::QueryRays q, int64_t n, int K, const mrt::Neighbours& out) {
+    pointChunks(r, q, n, "mrt_neighbours_device",
+                [&](const mrt::Level& lv, const mrt::QueryTables& tb, const float* dist, int64_t base, int m, int threads,
+                    hipStream_t st) {
+                    mrt::launchNeighbourWalk(r->ds, lv, r->pipe.counters, r->pipe.gstack, r->gdepth, tb, dist, base, m, K,
+                                             out, threads, st);
+                });
 }
 
 // ---- shaded ray queries (mrt_shade_rays_device) ------------------------------------------------
@@ -2411,6 +2467,26 @@ int mrt_nearest_points_device(mrt_renderer* r, const mrt_point_batch* pts, const
             MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
         }
         nearestPoints(r, q, pts->n, nr);
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinOut, r->stream));
+            MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
+        }
+    });
+}
+
+int mrt_neighbours_device(mrt_renderer* r, const mrt_point_batch* pts, int32_t K, const mrt_neighbours* out, size_t outSize,
+                          void* stream) {
+    return guarded([&] {
+        mrt::Neighbours nb{};
+        const mrt::QueryRays q = checkNeighbourBatch(r, pts, K, out, outSize, &nb);
+        MRT_HIP(hipSetDevice(r->device));
+        hipStream_t st = stream != nullptr ? static_cast<hipStream_t>(stream) : r->stream;
+        // joined to the caller's stream on both sides, as mrt_cast_rays_device
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinIn, st));
+            MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
+        }
+        neighbourPoints(r, q, pts->n, K, nb);
         if (st != r->stream) {
             MRT_HIP(hipEventRecord(r->joinOut, r->stream));
             MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
