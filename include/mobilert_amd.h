@@ -30,6 +30,8 @@
  *                             answers questions about rays only); mrt_point_distance is its definition on the host
  *   mrt_neighbours_device     the K nearest surfaces to each of the caller's points, in order, and the number
  *                             within the point's radius (no reference call)
+ *   mrt_overlap_boxes_device  the surfaces touching each of the caller's boxes, in order, and their number
+ *                             (no reference call); mrt_box_overlap is its definition on the host
  *   mrt_scene_triangles / _planes / _spheres / _materials / _lights
  *                             Shader::getTriangles / getPlanes / getSpheres / getMaterials / getLights
  *                             (Shader.hpp:92-100) in the scene's input order
@@ -711,6 +713,75 @@ typedef struct mrt_neighbours {   /* packed device arrays or NULL (not wanted); 
 } mrt_neighbours;
 int mrt_neighbours_device(mrt_renderer *r, const mrt_point_batch *pts, int32_t K,
                           const mrt_neighbours *out, size_t outSize, void *stream);
+
+/* ---- overlap queries (on the GPU; beyond the reference's entry points) ----
+ * mrt_overlap_boxes_device: for each axis-aligned box of a caller-supplied batch the surfaces of the loaded
+ * scene that touch it, and their number: what is inside a voxel, which faces a link's bounding box
+ * touches, whether a cell of an occupancy grid is empty, which triangles fall in a selection marquee.
+ *
+ * The definition.  A candidate is accepted when its kind's overlap function returns true; mrt_box_overlap
+ * evaluates those functions on the host, and the kernels compile the same source without contraction, so
+ * the bits agree.  Triangles and area lights: boxTriangle(A, AB, AC, mn, mx), a 13-axis separating-axis
+ * test on the corners A, A + AB, A + AC with slacks that keep every real overlap; planes: boxPlane;
+ * spheres: boxSphere, the sphere's surface (a box wholly inside a sphere does not touch it).  The order
+ * of operations, the slacks and their argument are written in csrc/mrt_overlap.hpp.  The contract, on
+ * valid finite input: (a) if the primitive and the closed box overlap in exact arithmetic on the stored
+ * float32 values, the function returns true (touching counts; slivers, segments and points included);
+ * (b) if it returns true, the primitive overlaps the box grown by g * 2^-24 * M on every side, M the
+ * largest |coordinate| involved, g = 64 as measured (tests/test_overlap_cpu.py pins 4 g).  The
+ * reference's Triangle::intersect(const AABB&) is not the definition: it treats edges as half-lines and
+ * accepts any triangle whose plane is parallel to the box diagonal.
+ *
+ * Candidates are exactly those of mrt_neighbours_device: BVH (3) and Naive (1): every plane, sphere,
+ * triangle and area light; an accelerator id that builds nothing: the area lights only; point lights
+ * never.  There is no src: a box leaves no primitive.
+ * any[i] is 1 if anything is accepted, else 0.  count[i] is the number of accepted candidates, not capped
+ * by K.  The list is the first min(count, K) accepted candidates ordered by kind (plane, sphere,
+ * triangle, light), then by INPUT index; entries count .. K - 1 are padding: kind 0, index -1.  BVH and
+ * Naive agree bit for bit in every field but tests, and every entry is what mrt_box_overlap says of that
+ * pair.  An invalid box (a bound that is not finite, or mn > mx on some axis) accepts nothing: any 0,
+ * count 0, every entry padding; mn == mx is valid.  A primitive with a non-finite corner is never accepted.
+ *
+ * What the walk may skip.  Under BVH a node of the reference tree is skipped only when node.mn.a > mx.a or
+ * node.mx.a < mn.a on some axis, strict and false for NaN: the overlap function's own first step on a box
+ * that contains the triangle's hull, so nothing accepted is lost and no certified bound is needed.  (The
+ * builder's boxes contain the hull of every finite triangle unless the scene holds a triangle whose first
+ * corner has a NaN coordinate; csrc/mrt_overlap.hpp.)  What a call costs depends on the outputs:
+ *   only any wanted (count, kind and index NULL, whatever K): the walk stops at a box's first acceptance
+ *                      - the occupancy test, and the cheap form.
+ *   anything else:     every accepted candidate is met, because the K smallest input indices cannot be
+ *                      known otherwise.  A box that contains the scene costs what Naive costs; that is
+ *                      allowed.
+ * tests[i] counts the overlap-function evaluations made for box i (diagnostic; it differs between
+ * accelerators and between the two forms, and does not change the form).
+ * RegularGrid (accelerator 2) and device groups are refused as for every point query: -1 with a message,
+ * nothing done.  Everything else as mrt_neighbours_device: stream order and no host synchronisation; no
+ * allocation after a renderer's first query (the walk writes the caller's arrays itself); chunks of
+ * rayCap[0]; state (later frames, views and queries keep their bits and counts; the totals and frame
+ * statistics do not see the call); outSize (fields beyond it count as NULL; fields are only ever
+ * appended).  Argument errors (a NULL handle, batch, mn, mx or out; K outside 1 .. MRT_OVERLAP_MAX; n
+ * outside 1 .. 2^31 - 1; a stride of 1, 2 or below 0; outSize too small to hold any; every field within
+ * outSize NULL) return -1 before any device work, with a message in mrt_last_error(); they are checked
+ * before the renderer is read.
+ * mrt_box_overlap (host only) / mrt_kat_box_overlap (the same pairs through the device's functions; needs
+ * a GPU): pair i of a kind - mrt_point_distance's kinds and primitive layouts - against the box (mn xyz,
+ * mx xyz) at boxes + 6 i; out[i] = 1 accepted, 0 not. */
+#define MRT_OVERLAP_MAX 16
+typedef struct mrt_box_batch {
+    const float *mn, *mx;       /* device: box i's min xyz at mn + i * mnStride, max at mx + i * mxStride */
+    int64_t mnStride, mxStride; /* floats, >= 3; 0 means 3.  6 and mx = mn + 3 read an (n, 6) array */
+    int64_t n;                  /* 1 .. 2^31 - 1 */
+} mrt_box_batch;
+typedef struct mrt_overlaps {   /* packed device arrays or NULL (not wanted); fields only ever appended */
+    int32_t *any;               /* n: 1 if anything is accepted, else 0 */
+    int32_t *count;             /* n: accepted candidates, not capped by K */
+    int32_t *kind, *index;      /* n x K, entry k of box i at i * K + k; padding kind 0, index -1 */
+    int32_t *tests;             /* n: overlap-function evaluations made for box i (diagnostic) */
+} mrt_overlaps;
+int mrt_overlap_boxes_device(mrt_renderer *r, const mrt_box_batch *boxes, int32_t K,
+                             const mrt_overlaps *out, size_t outSize, void *stream);
+int mrt_box_overlap(int32_t kind, const float *prims, const float *boxes, int64_t n, int32_t *out);     /* host only */
+int mrt_kat_box_overlap(int32_t kind, const float *prims, const float *boxes, int32_t n, int32_t *out); /* needs a GPU */
 
 /* ---- shaded ray queries (on the GPU; beyond the reference's entry points) ----
  * mrt_shade_rays_device: the radiance that arrives along each ray of a caller-supplied batch, as

@@ -568,6 +568,79 @@ class Renderer:
                                    **{"d_" + name: x.data_ptr() for name, x in out.items()})
         return out
 
+    # -- overlap queries -----------------------------------------------------------------
+    OVERLAP_FIELDS = tuple(name for name, _, _ in _native.OVERLAP_FIELDS)
+
+    def overlap_boxes_device(self, d_mn: int, d_mx: int, n: int, k: int, /, *, mn_stride: int = 3, mx_stride: int = 3,
+                             stream: int = 0, out_size: Optional[int] = None, **fields: int) -> None:
+        """mrt_overlap_boxes_device: the surfaces touching each of ``n`` axis-aligned boxes resident in device
+        memory (box i's min xyz at ``d_mn`` + i * ``mn_stride`` floats, its max at ``d_mx`` + i *
+        ``mx_stride``), the first ``k`` (1 .. 16) by kind and input index, and their number.  ``fields``:
+        ``d_any``, ``d_count``, ``d_tests`` (n int32), ``d_kind`` / ``d_index`` (n x k int32) - device
+        pointers as ints to packed arrays (mrt_overlaps), 0 or absent: not wanted.  With ``d_any`` alone
+        (``d_tests`` aside) the walk stops at a box's first acceptance.  ``out_size`` and ``stream`` as for
+        neighbours_device."""
+        out = _native.MrtOverlaps()
+        for key, value in fields.items():
+            if not key.startswith("d_") or key[2:] not in self.OVERLAP_FIELDS:
+                raise TypeError("overlap_boxes_device: unknown output %r" % key)
+            setattr(out, key[2:], value or None)
+        batch = _native.MrtBoxBatch(d_mn or None, d_mx or None, int(mn_stride), int(mx_stride), int(n))
+        size = ctypes.sizeof(out) if out_size is None else int(out_size)
+        _native.check(self._lib.mrt_overlap_boxes_device(self._h, ctypes.byref(batch), int(k), ctypes.byref(out), size,
+                                                         ctypes.c_void_p(stream or None)))
+
+    def overlap_boxes(self, mn, mx, k: int, fields=None):
+        """overlap_boxes_device for torch tensors on the renderer's device: ``mn`` / ``mx`` float32 (n, >= 3)
+        (two column slices of one (n, 6) tensor are read in place), with cast_rays' stream joining.  Returns
+        a dict of tensors, one per name in ``fields`` (None: all of ``Renderer.OVERLAP_FIELDS``): int32
+        ``any`` / ``count`` / ``tests`` (n,) and ``kind`` / ``index`` (n, k), allocated and ordered on torch's
+        current stream.  ``fields=("any",)`` is the occupancy test.  An empty batch returns empty tensors."""
+        import torch
+
+        device, n, mn, mn_stride, mx, mx_stride = self._ray_tensors(mn, mx)
+        k = int(k)
+        if not 1 <= k <= _native.OVERLAP_MAX:
+            raise ValueError("k: 1 .. %d" % _native.OVERLAP_MAX)
+        fields = self.OVERLAP_FIELDS if fields is None else tuple(fields)
+        if not fields or any(f not in self.OVERLAP_FIELDS for f in fields):
+            raise ValueError("fields: at least one of %s" % (self.OVERLAP_FIELDS,))
+        out = {}
+        for name, dtype, width in _native.OVERLAP_FIELDS:
+            if name in fields:
+                out[name] = torch.empty((n,) if width == 0 else (n, k), dtype=getattr(torch, dtype), device=device)
+        if n == 0:
+            return out
+        with self._query_stream_of(device) as stream:
+            self.overlap_boxes_device(mn.data_ptr(), mx.data_ptr(), n, k, mn_stride=mn_stride, mx_stride=mx_stride,
+                                      stream=stream, **{"d_" + name: x.data_ptr() for name, x in out.items()})
+        return out
+
+    def voxel_occupancy(self, origin, cell, dims, field: str = "any"):
+        """One overlap query (k = 1, the one ``field``: "any", "count" or "tests") over the cells of a lattice:
+        ``dims`` = (nx, ny, nz) cells of size ``cell`` (a number or three) from ``origin``.  Cell (ix, iy, iz)
+        has mn = origin + cell * (ix, iy, iz) and mx = origin + cell * (ix + 1, iy + 1, iz + 1) in float32, one
+        multiplication and one addition, so neighbouring cells share their faces bit for bit and a triangle
+        lying in a shared face is in both cells.  Returns an int32 (nz, ny, nx) tensor on the renderer's GPU."""
+        import torch
+
+        if field not in ("any", "count", "tests"):
+            raise ValueError('field: "any", "count" or "tests"')
+        nx, ny, nz = (int(d) for d in dims)
+        if min(nx, ny, nz) < 1:
+            raise ValueError("dims: three positive cell counts")
+        device = torch.device("cuda", self.config.device if self.config.device >= 0 and not self.config.devices
+                              else torch.cuda.current_device())
+        o = torch.tensor([float(x) for x in origin], dtype=torch.float32, device=device)
+        c = torch.tensor([float(x) for x in (cell if hasattr(cell, "__len__") else (cell,) * 3)], dtype=torch.float32,
+                         device=device)
+        iz, iy, ix = torch.meshgrid(torch.arange(nz, device=device), torch.arange(ny, device=device),
+                                    torch.arange(nx, device=device), indexing="ij")
+        idx = torch.stack((ix, iy, iz), dim=-1).reshape(-1, 3).to(torch.float32)
+        mn = o + c * idx
+        mx = o + c * (idx + 1.0)
+        return self.overlap_boxes(mn, mx, 1, fields=(field,))[field].reshape(nz, ny, nx)
+
     def first_hit_planes(self, camera=None, sample: int = 0, fields=None):
         """The first hit of every pixel's camera ray (sample ``sample``) as planes: camera_rays(camera,
         sample_base=sample, spp=1), then cast_hits, scattered by ``pixels`` into (height, width) or
@@ -915,6 +988,29 @@ def point_distance(kind, prims, points):
 def kat_point_distance(kind, prims, points):
     """The same pairs through the device's distance functions (needs a GPU)."""
     return _point_distance(_native.lib().mrt_kat_point_distance, kind, prims, points)
+
+
+def _box_overlap(fn, kind, prims, boxes):
+    kind = int(kind)
+    width = {1: 6, 2: 4, 3: 9, 4: 9}.get(kind, 9)
+    pr = np.ascontiguousarray(prims, np.float32).reshape(-1, width)
+    bx = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
+    if len(pr) != len(bx):
+        raise ValueError("box_overlap: as many primitives as boxes")
+    out = np.empty(len(bx), np.int32)
+    _native.check(fn(kind, _ptr(pr), _ptr(bx), len(bx), _ptr(out)))
+    return out
+
+
+def box_overlap(kind, prims, boxes):
+    """mrt_box_overlap (host, no GPU): the overlap query's functions on (primitive, box) pairs.  kind and
+    prims as for point_distance; boxes (n, 6): min xyz, max xyz.  Returns int32 (n,): 1 accepted, 0 not."""
+    return _box_overlap(_native.lib().mrt_box_overlap, kind, prims, boxes)
+
+
+def kat_box_overlap(kind, prims, boxes):
+    """The same pairs through the device's overlap functions (needs a GPU)."""
+    return _box_overlap(_native.lib().mrt_kat_box_overlap, kind, prims, boxes)
 
 
 def kat_accumulate(rgb, spp, sample_base, bitmap, width, height, mode=0):

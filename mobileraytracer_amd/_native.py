@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = (
     "mrt_path_key", "mrt_shade_rays_device", "mrt_camera_rays_device",
     "mrt_cast_hits_device", "mrt_cast_multi_hits_device", "mrt_scene_triangles", "mrt_scene_planes", "mrt_scene_spheres", "mrt_scene_materials",
     "mrt_scene_lights", "mrt_nearest_points_device", "mrt_point_distance", "mrt_kat_point_distance",
-    "mrt_neighbours_device",
+    "mrt_neighbours_device", "mrt_overlap_boxes_device", "mrt_box_overlap", "mrt_kat_box_overlap",
     "RayTrace", "stopRender",
 )
 
@@ -112,6 +112,22 @@ NEIGHBOUR_FIELDS = (("count", "int32", 0), ("kind", "int32", 1), ("index", "int3
 
 class MrtNeighbours(ctypes.Structure):  # mrt_neighbours: device arrays of a neighbour query, NULL = not wanted
     _fields_ = [(name, ctypes.c_void_p) for name, _, _ in NEIGHBOUR_FIELDS]
+
+
+OVERLAP_MAX = 16  # MRT_OVERLAP_MAX
+# mrt_overlaps: the fields in the header's order, (name, dtype, entries per box: 0 = one per box, else ints
+# per list entry)
+OVERLAP_FIELDS = (("any", "int32", 0), ("count", "int32", 0), ("kind", "int32", 1), ("index", "int32", 1),
+                  ("tests", "int32", 0))
+
+
+class MrtBoxBatch(ctypes.Structure):  # mrt_box_batch: a device-resident batch of boxes (mrt_overlap_boxes_device)
+    _fields_ = [("mn", ctypes.c_void_p), ("mx", ctypes.c_void_p), ("mnStride", ctypes.c_int64),
+                ("mxStride", ctypes.c_int64), ("n", ctypes.c_int64)]
+
+
+class MrtOverlaps(ctypes.Structure):  # mrt_overlaps: device arrays of an overlap query, NULL = not wanted
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in OVERLAP_FIELDS]
 
 
 class MrtShadeBatch(ctypes.Structure):  # mrt_shade_batch: rays and their path keys (mrt_shade_rays_device)
@@ -262,6 +278,10 @@ def load_library(path=LIB_PATH):
         "mrt_nearest_points_device": (ctypes.c_int, [vp, P(MrtPointBatch), P(MrtNearest), ctypes.c_size_t, vp]),
         "mrt_neighbours_device": (ctypes.c_int, [vp, P(MrtPointBatch), ctypes.c_int32, P(MrtNeighbours),
                                                  ctypes.c_size_t, vp]),
+        "mrt_overlap_boxes_device": (ctypes.c_int, [vp, P(MrtBoxBatch), ctypes.c_int32, P(MrtOverlaps),
+                                                    ctypes.c_size_t, vp]),
+        "mrt_box_overlap": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int64, vp]),
+        "mrt_kat_box_overlap": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int32, vp]),
         "mrt_point_distance": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int64, vp, vp, vp]),
         "mrt_kat_point_distance": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int32, vp, vp, vp]),
         "mrt_scene_triangles": (ctypes.c_int64, [vp, vp, vp, vp, vp]),
@@ -299,7 +319,7 @@ def source_stamp():
     srcs = ["mrt_scene.cpp", "mrt_grid.cpp", "mrt_texture.cpp", "mrt_android.cpp", "mrt_queue_plan.cpp", "mrt_kernels.hip",
             "mrt_renderer.hip",
             "mrt_common.hpp", "mrt_device.hpp", "mrt_kernels.hpp", "mrt_trace_ww.hpp", "mrt_trace_packet.hpp",
-            "mrt_multi_hit.hpp", "mrt_nearest.hpp", "mrt_neighbours.hpp", "mrt_scene.hpp", "mrt_queue_plan.hpp", "../../include/mobilert_amd.h", "../../include/mobilert_amd.hpp",
+            "mrt_multi_hit.hpp", "mrt_nearest.hpp", "mrt_neighbours.hpp", "mrt_overlap.hpp", "mrt_scene.hpp", "mrt_queue_plan.hpp", "../../include/mobilert_amd.h", "../../include/mobilert_amd.hpp",
             "../../include/mobilert_android.h"]
     h = hashlib.sha256()
     for f in srcs:

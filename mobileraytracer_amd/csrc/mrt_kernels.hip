@@ -22,6 +22,7 @@
 #include "mrt_multi_hit.hpp"
 #include "mrt_nearest.hpp"
 #include "mrt_neighbours.hpp"
+#include "mrt_overlap.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1739,6 +1740,78 @@ void launchNeighbourWalk(const DScene& s, const Level& lv, int* counters, int2* 
     }
 #undef MRT_LAUNCH_NEIGHBOUR_K
 #undef MRT_LAUNCH_NEIGHBOUR
+}
+
+// ---------------------------------------------------------------------------------------
+// Overlap queries (mrt_overlap_boxes_device).  k_overlap_walk: k_neighbour_walk's frame - one box per
+// lane, a wave taking 64 boxes at a time from level 1's fetch cursor, the lane writing the caller's arrays
+// itself - around the walk of mrt_overlap.hpp.  k_query_load put each box's mn into the origin slots and
+// its mx into the direction slots; no source is carried.  The stack holds references only (RefStack, 16
+// entries of 4 B per lane in LDS = 4 KB, deeper ones in the closest-hit walk's spill area, as k_multi_walk).
+// kCeil: the list's size in LDS (1, 4 or 16 entries of 4 B per lane); kAny: only `any` is wanted, so there
+// is no list and the walk stops at the lane's first acceptance.  K is the caller's (the entries' stride);
+// listK the entries held (K, or 0 where neither kind nor index is wanted).
+template <int kCeil, bool kAny>
+__global__ __launch_bounds__(kOverlapThreads) void k_overlap_walk(DScene s, Level lv, int* counters, int2* gstack,
+                                                                  int gdepth, QueryTables tb, long long base, int K,
+                                                                  int listK, Overlaps out) {
+    __shared__ int ldsStack[RefStack<kOverlapThreads>::kDepth * kOverlapThreads];
+    __shared__ uint32_t olCode[kCeil * kOverlapThreads];
+    auto st = makeRefStack<kOverlapThreads>(reinterpret_cast<int2*>(ldsStack), gstack, gdepth);
+    OverlapHeld<kAny> ol{olCode + threadIdx.x, min(listK, kCeil), 0, 0, 0};
+    const SegMap map = segMap(counters, 1, false, lv.segCap);
+    int* fetch = counters + kCntFetchShards + 1 * kMaxFetchShards * kFetchStride;
+    while (true) {
+        int first = 0;
+        if (laneId() == 0) first = atomicAdd(fetch, 64);
+        first = __shfl(first, 0, 64);
+        if (first >= map.total()) break;
+        const int v = first + laneId();
+        if (v < map.total()) {
+            const int i = map.phys(v);
+            const long long g = base + i;  // the box's index in the caller's batch (k_query_load put it at i)
+            ol.reset();
+            overlapBox(s, tb, xyz(lv.rO[i]), xyz(lv.rD[i]), ol, st);
+            if (out.any != nullptr) out.any[g] = ol.count != 0 ? 1 : 0;
+            if (out.tests != nullptr) out.tests[g] = ol.tests;
+            if (!kAny) {
+                if (out.count != nullptr) out.count[g] = ol.count;
+                const long long e0 = g * K;
+                for (int k = 0; k < ol.K; ++k) {
+                    const bool held = k < ol.n;
+                    const uint32_t code = held ? ol.code[k * kOverlapThreads] : kNoPrim;
+                    if (out.kind != nullptr) out.kind[e0 + k] = static_cast<int32_t>(primKind(code));
+                    if (out.index != nullptr) out.index[e0 + k] = held ? static_cast<int32_t>(primIndex(code)) : -1;
+                }
+            }
+        }
+    }
+}
+
+void launchOverlapWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth, const QueryTables& tb,
+                       long long base, int n, int K, const Overlaps& out, int maxThreads, hipStream_t st) {
+    // a persistent grid over the fetch cursor: a wave per 64 boxes, at most the threads the spill area holds
+    const dim3 blocks(std::max(1, std::min(maxThreads / kOverlapThreads, (n + kOverlapThreads - 1) / kOverlapThreads)));
+    const bool list = out.kind != nullptr || out.index != nullptr;
+    const int listK = list ? K : 0;
+#define MRT_LAUNCH_OVERLAP(CEIL, ANY) \
+    hipLaunchKernelGGL((k_overlap_walk<CEIL, ANY>), blocks, dim3(kOverlapThreads), 0, st, s, lv, counters, gstack, gdepth, tb, base, K, listK, out)
+    if (!list && out.count == nullptr) MRT_LAUNCH_OVERLAP(1, true);
+    else if (listK <= 1) MRT_LAUNCH_OVERLAP(1, false);
+    else if (listK <= 4) MRT_LAUNCH_OVERLAP(4, false);
+    else MRT_LAUNCH_OVERLAP(kOverlapMax, false);
+#undef MRT_LAUNCH_OVERLAP
+}
+
+__global__ __launch_bounds__(64) void k_kat_box_overlap(int kind, const float* prims, const float* boxes, int n,
+                                                        int32_t* out) {
+    const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    out[i] = overlapPrim(kind, prims + static_cast<long long>(i) * pointPrimFloats(kind), boxes + 6LL * i) ? 1 : 0;
+}
+
+void launchKatBoxOverlap(int kind, const float* prims, const float* boxes, int n, int32_t* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_kat_box_overlap, dim3((n + 63) / 64), dim3(64), 0, st, kind, prims, boxes, n, out);
 }
 
 __global__ __launch_bounds__(64) void k_kat_point_distance(int kind, const float* prims, const float* points, int n,

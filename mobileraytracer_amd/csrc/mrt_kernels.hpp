@@ -386,6 +386,25 @@ struct Neighbours {
 void launchNeighbourWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth, const QueryTables& tb,
                          const float* dist, long long base, int n, int K, const Neighbours& out, int maxThreads,
                          hipStream_t st);
+// Overlap queries (mrt_overlap_boxes_device): the device arrays of mrt_overlaps, packed (box g's any, count
+// and tests at g, its entry k at g * K + k) or null (not wanted: not stored).
+constexpr int kOverlapMax = 16;  // MRT_OVERLAP_MAX: the largest list
+struct Overlaps {
+    int32_t* any;
+    int32_t* count;
+    int32_t* kind;
+    int32_t* index;
+    int32_t* tests;
+};
+// k_overlap_walk (mrt_overlap.hpp): the n boxes k_query_load put into lv's queue (mn the origins, mx the
+// directions), each box's first K accepted candidates (K 1 .. 16) in (kind, input index) order, its count
+// and the padding stored by the walk itself at base + i.  Where count, kind and index are all null the walk
+// stops at a lane's first acceptance (the occupancy test); the spill area is the closest-hit walk's.
+void launchOverlapWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth, const QueryTables& tb,
+                       long long base, int n, int K, const Overlaps& out, int maxThreads, hipStream_t st);
+// known answers: pair i (kind's record at prims + i * pointPrimFloats(kind), box at boxes + 6 i) through the
+// device's overlap functions
+void launchKatBoxOverlap(int kind, const float* prims, const float* boxes, int n, int32_t* out, hipStream_t st);
 // known answers: pair i (kind's record at prims + i * pointPrimFloats(kind), point at points + 3 i)
 // through the device's distance functions
 void launchKatPointDistance(int kind, const float* prims, const float* points, int n, float* dist2, float* nearest,

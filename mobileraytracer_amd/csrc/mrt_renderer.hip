@@ -27,6 +27,7 @@
 #include "mobilert_amd.hpp"
 #include "mrt_kernels.hpp"
 #include "mrt_nearest.hpp"
+#include "mrt_overlap.hpp"
 #include "mrt_queue_plan.hpp"
 #include "mrt_scene.hpp"
 
@@ -2149,6 +2150,49 @@ void neighbourPoints(mrt_renderer* r, mrt::QueryRays q, int64_t n, int K, const 
                 });
 }
 
+// ---- overlap queries (mrt_overlap_boxes_device) ------------------------------------------------
+// The argument checks, as checkNeighbourBatch's: the batch, K and the outputs before the renderer is read.
+mrt::QueryRays checkBoxBatch(const mrt_renderer* r, const mrt_box_batch* boxes, int32_t K, const mrt_overlaps* out,
+                             size_t outSize, mrt::Overlaps* ov) {
+    if (r == nullptr) throw std::runtime_error("mrt_overlap_boxes_device: null renderer");
+    if (boxes == nullptr) throw std::runtime_error("mrt_overlap_boxes_device: null box batch");
+    if (boxes->mn == nullptr || boxes->mx == nullptr) throw std::runtime_error("mrt_overlap_boxes_device: null mn / mx");
+    if (out == nullptr) throw std::runtime_error("mrt_overlap_boxes_device: null outputs");
+    if (K < 1 || K > MRT_OVERLAP_MAX)
+        throw std::runtime_error("mrt_overlap_boxes_device: K must be 1 .. " + std::to_string(MRT_OVERLAP_MAX));
+    static_assert(MRT_OVERLAP_MAX == mrt::kOverlapMax, "the list's largest instantiation holds the header's K");
+    if (outSize < offsetof(mrt_overlaps, any) + sizeof(out->any))
+        throw std::runtime_error("mrt_overlap_boxes_device: outSize too small to hold any");
+    static_assert(sizeof(mrt_overlaps) == 5 * sizeof(void*), "mrt_overlaps: pointers only (fields are appended)");
+    mrt_overlaps o{};
+    std::memcpy(&o, out, std::min(outSize, sizeof(o)) / sizeof(void*) * sizeof(void*));
+    *ov = mrt::Overlaps{o.any, o.count, o.kind, o.index, o.tests};
+    if (o.any == nullptr && o.count == nullptr && o.kind == nullptr && o.index == nullptr && o.tests == nullptr)
+        throw std::runtime_error("mrt_overlap_boxes_device: no output (every field within outSize is null)");
+    if (boxes->n < 1 || boxes->n > 0x7fffffffLL) throw std::runtime_error("mrt_overlap_boxes_device: n must be 1 .. 2^31 - 1");
+    if ((boxes->mnStride != 0 && boxes->mnStride < 3) || (boxes->mxStride != 0 && boxes->mxStride < 3))
+        throw std::runtime_error("mrt_overlap_boxes_device: strides must be 0 (packed) or >= 3 floats");
+    mrt::QueryRays q{};
+    q.orig = boxes->mn;
+    q.dir = boxes->mx;
+    q.origStride = boxes->mnStride == 0 ? 3 : boxes->mnStride;
+    q.dirStride = boxes->mxStride == 0 ? 3 : boxes->mxStride;
+    if (!r->peers.empty()) throw std::runtime_error("mrt_overlap_boxes_device: device groups are not supported for queries");
+    if (r->ds.accel == mrt::kAccGrid)
+        throw std::runtime_error("mrt_overlap_boxes_device: the RegularGrid accelerator (2) is not supported: the "
+                                 "region queries walk the reference tree");
+    return q;
+}
+
+void overlapBoxes(mrt_renderer* r, mrt::QueryRays q, int64_t n, int K, const mrt::Overlaps& out) {
+    pointChunks(r, q, n, "mrt_overlap_boxes_device",
+                [&](const mrt::Level& lv, const mrt::QueryTables& tb, const float*, int64_t base, int m, int threads,
+                    hipStream_t st) {
+                    mrt::launchOverlapWalk(r->ds, lv, r->pipe.counters, r->pipe.gstack, r->gdepth, tb, base, m, K, out,
+                                           threads, st);
+                });
+}
+
 // ---- shaded ray queries (mrt_shade_rays_device) ------------------------------------------------
 // The argument checks, all before any device work, in checkRayBatch's order: the batch and the
 // output first (those checks do not read the renderer).
@@ -2487,6 +2531,26 @@ int mrt_neighbours_device(mrt_renderer* r, const mrt_point_batch* pts, int32_t K
             MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
         }
         neighbourPoints(r, q, pts->n, K, nb);
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinOut, r->stream));
+            MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
+        }
+    });
+}
+
+int mrt_overlap_boxes_device(mrt_renderer* r, const mrt_box_batch* boxes, int32_t K, const mrt_overlaps* out,
+                             size_t outSize, void* stream) {
+    return guarded([&] {
+        mrt::Overlaps ov{};
+        const mrt::QueryRays q = checkBoxBatch(r, boxes, K, out, outSize, &ov);
+        MRT_HIP(hipSetDevice(r->device));
+        hipStream_t st = stream != nullptr ? static_cast<hipStream_t>(stream) : r->stream;
+        // joined to the caller's stream on both sides, as mrt_cast_rays_device
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinIn, st));
+            MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
+        }
+        overlapBoxes(r, q, boxes->n, K, ov);
         if (st != r->stream) {
             MRT_HIP(hipEventRecord(r->joinOut, r->stream));
             MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
@@ -3267,6 +3331,31 @@ int mrt_kat_point_distance(int32_t kind, const float* prims, const float* points
         if (dist2 != nullptr) MRT_HIP(hipMemcpy(dist2, d.p, N * 4, hipMemcpyDeviceToHost));
         if (nearest != nullptr) MRT_HIP(hipMemcpy(nearest, q.p, N * 12, hipMemcpyDeviceToHost));
         if (bary != nullptr) MRT_HIP(hipMemcpy(bary, uv.p, N * 8, hipMemcpyDeviceToHost));
+        MRT_HIP(hipDeviceSynchronize());
+    });
+}
+
+int mrt_box_overlap(int32_t kind, const float* prims, const float* boxes, int64_t n, int32_t* out) {
+    return guarded([&] {
+        checkPointPairs("mrt_box_overlap", kind, prims, boxes, n);
+        if (out == nullptr) throw std::runtime_error("mrt_box_overlap: null out");
+        const int w = mrt::pointPrimFloats(kind);
+        for (int64_t i = 0; i < n; ++i) out[i] = mrt::overlapPrim(kind, prims + i * w, boxes + 6 * i) ? 1 : 0;
+    });
+}
+
+int mrt_kat_box_overlap(int32_t kind, const float* prims, const float* boxes, int32_t n, int32_t* out) {
+    return guarded([&] {
+        checkPointPairs("mrt_kat_box_overlap", kind, prims, boxes, n);
+        if (out == nullptr) throw std::runtime_error("mrt_kat_box_overlap: null out");
+        if (n == 0) return;
+        const size_t N = static_cast<size_t>(n), w = static_cast<size_t>(mrt::pointPrimFloats(kind));
+        DevBuf p(N * w * 4), b(N * 24), o(N * 4);
+        MRT_HIP(hipMemcpy(p.p, prims, N * w * 4, hipMemcpyHostToDevice));
+        MRT_HIP(hipMemcpy(b.p, boxes, N * 24, hipMemcpyHostToDevice));
+        mrt::launchKatBoxOverlap(kind, p.as<float>(), b.as<float>(), n, o.as<int32_t>(), nullptr);
+        MRT_HIP(hipGetLastError());
+        MRT_HIP(hipMemcpy(out, o.p, N * 4, hipMemcpyDeviceToHost));
         MRT_HIP(hipDeviceSynchronize());
     });
 }
