@@ -32,6 +32,8 @@
  *                             within the point's radius (no reference call)
  *   mrt_overlap_boxes_device  the surfaces touching each of the caller's boxes, in order, and their number
  *                             (no reference call); mrt_box_overlap is its definition on the host
+ *   mrt_sweep_spheres_device  the first contact of a sphere moving along each of the caller's rays (no
+ *                             reference call); mrt_sphere_sweep is its definition on the host
  *   mrt_scene_triangles / _planes / _spheres / _materials / _lights
  *                             Shader::getTriangles / getPlanes / getSpheres / getMaterials / getLights
  *                             (Shader.hpp:92-100) in the scene's input order
@@ -782,6 +784,86 @@ int mrt_overlap_boxes_device(mrt_renderer *r, const mrt_box_batch *boxes, int32_
                              const mrt_overlaps *out, size_t outSize, void *stream);
 int mrt_box_overlap(int32_t kind, const float *prims, const float *boxes, int64_t n, int32_t *out);     /* host only */
 int mrt_kat_box_overlap(int32_t kind, const float *prims, const float *boxes, int32_t n, int32_t *out); /* needs a GPU */
+
+/* ---- sweep queries (on the GPU; beyond the reference's entry points) ----
+ * mrt_sweep_spheres_device: for each ray of a caller-supplied batch, how far a sphere of the ray's radius
+ * can move along it before it touches a surface of the loaded scene, and where it touches: the shape cast
+ * of capsule and character controllers, the "is this move free" test of a motion planner, continuous
+ * collision detection for a bounding sphere.  With ray casts and overlaps it completes the three questions
+ * such callers ask of a scene.
+ *
+ * The motion.  The centre of sweep i is c(t) = orig_i + dir_i * t in float32, one multiply and one add per
+ * component; dir is taken as given, not normalised, so with dir = goal - start t is the fraction of the
+ * motion.  d_radius[i] is the radius.  Valid input: orig, dir and radius finite, radius >= 0; anything else
+ * accepts nothing.  dir == 0 is valid (only a start in contact is found); radius == 0 is a moving point,
+ * whose answer is this query's own and not the bits of mrt_cast_rays_device.
+ *
+ * The definition.  A candidate's first-contact time is its kind's sweep function; mrt_sphere_sweep evaluates
+ * those functions on the host, and the kernels compile the same source without contraction, so the bits
+ * agree.  Triangles and area lights: sweepTriangle(A, AB, AC, o, d, r) - t = 0 where the distance at o is
+ * within r, else the least of up to seven candidate times (the face's plane, the three edges' lines, the three
+ * corners, in closest-approach form) that the distance function confirms: its d2 at c(t) <= acc2,
+ * acc = r (1 + 2^-20) + 32 * 2^-24 * M, M the largest |coordinate| involved (the distance function is
+ * pointTriangle's record unless an edge's or the face's own is nearer, which keeps thin triangles exact); planes: sweepPlane; spheres:
+ * sweepSphere, the sphere's surface (a sphere inside a sphere moves until it touches the surface from
+ * within).  The order of operations, the slack and their argument are written in csrc/mrt_sweep.hpp.  The
+ * contract, on valid finite input against an exact evaluation on the stored float32 values, M including
+ * the radius: (a) never late - the returned t is at most the exact first-contact time of the sphere shrunk
+ * to radius r - g * 2^-24 * M; (b) never early - at a returned hit the exact distance from the reported
+ * centre to the primitive is at most r + g * 2^-24 * M; g = 64 as measured (tests/test_sweep_cpu.py pins 4 g).
+ *
+ * The bound.  rays->dist[i] bounds t: dist[i] if > 0, else 0 (NaN included), +inf where dist is NULL.  A
+ * candidate is accepted when its t is below the bound and not NaN.
+ * Candidates and sources are those of mrt_nearest_points_device: BVH (3) and Naive (1): every plane,
+ * sphere, triangle and area light; an accelerator id that builds nothing: the area lights only; point
+ * lights never.  A src triangle or plane pair leaves that primitive out (a sphere resting on its source
+ * moves freely along it); a sphere or light pair changes nothing; a bad pair carries no source.
+ * The answer is the accepted candidate least by t; on bit-equal t (at t = 0 the common case: a sphere that
+ * starts touching several faces) by kind (plane, sphere, triangle, light), then by the lower INPUT index.
+ * So BVH and Naive agree bit for bit in every field but tests, and every field is what mrt_sphere_sweep
+ * gives for that pair.  hit 1, kind and index as mrt_nearest, t, centre = c(t), point = the contact point on
+ * the surface and bary = the distance function's record at c(t).  A miss writes hit 0, kind 0, index -1,
+ * t = the bound, and zeros.
+ *
+ * What the walk may skip.  Under BVH a node of the reference tree is skipped only when a conservatively
+ * rounded slab test finds no parameter in [0, min(bound, best t)] at which the centre is inside the node's
+ * box grown by the certified radius of csrc/mrt_sweep.hpp; every compare is strict and false for NaN, so
+ * an earlier-ordered tie still wins.  (As for the nearest-point cull, a scene that holds a triangle whose
+ * first corner has a NaN coordinate is outside the BVH = Naive guarantee.)  What a call costs depends on
+ * the outputs:
+ *   only hit wanted (tests aside): the walk stops at a ray's first acceptance - the motion planner's "is
+ *                      this move free" test, and the cheap form.
+ *   anything else:     the walk ends when no box within reach of the best t is left.
+ * tests[i] counts the sweep-function evaluations made for ray i (diagnostic; it differs between
+ * accelerators and between the two forms).
+ * RegularGrid (accelerator 2) and device groups are refused as for every point query: -1 with a message,
+ * nothing done.  Everything else as mrt_nearest_points_device: stream order and no host synchronisation; no
+ * allocation after a renderer's first query (the walk writes the caller's arrays itself); chunks of
+ * rayCap[0]; state (later frames, views and queries keep their bits and counts; the totals and frame
+ * statistics do not see the call); outSize (fields beyond it count as NULL; fields are only ever
+ * appended).  mrt_ray_batch is as for mrt_cast_rays_device and carries no radius: d_radius is n floats on
+ * the device.  Argument errors (a NULL handle, batch, orig, dir, d_radius or out; n outside 1 .. 2^31 - 1; a
+ * stride of 1, 2 or below 0; outSize too small to hold hit; every field within outSize NULL) return -1
+ * before any device work, with a message in mrt_last_error(); they are checked before the renderer is read.
+ * mrt_sphere_sweep (host only) / mrt_kat_sphere_sweep (the same pairs through the device's functions; needs
+ * a GPU): pair i of a kind - mrt_point_distance's kinds and primitive layouts - against the sweep (o xyz,
+ * d xyz, r) at rays + 7 i, unbounded; hit[i] 1 or 0, t[i] (+inf on a miss), centre, point and bary as above
+ * (zeros on a miss); a NULL output is not written. */
+typedef struct mrt_sweeps {      /* packed device arrays or NULL (not wanted); fields only ever appended */
+    int32_t *hit;                /* n: 1 if anything is accepted, else 0 */
+    int32_t *kind, *index;       /* n: as in mrt_nearest: 0 none, 1 plane .. 4 light; input order, -1 */
+    float   *t;                  /* n: the function's own bits; the bound on a miss */
+    float   *centre;             /* n x 3: c(t); 0, 0, 0 on a miss */
+    float   *point;              /* n x 3: the contact point on the surface; 0, 0, 0 on a miss */
+    float   *bary;               /* n x 2 */
+    int32_t *tests;              /* n: sweep-function evaluations made for ray i (diagnostic) */
+} mrt_sweeps;
+int mrt_sweep_spheres_device(mrt_renderer *r, const mrt_ray_batch *rays, const float *d_radius,
+                             const mrt_sweeps *out, size_t outSize, void *stream);
+int mrt_sphere_sweep(int32_t kind, const float *prims, const float *rays, int64_t n, int32_t *hit, float *t,
+                     float *centre, float *point, float *bary);          /* host only */
+int mrt_kat_sphere_sweep(int32_t kind, const float *prims, const float *rays, int32_t n, int32_t *hit,
+                         float *t, float *centre, float *point, float *bary);   /* needs a GPU */
 
 /* ---- shaded ray queries (on the GPU; beyond the reference's entry points) ----
  * mrt_shade_rays_device: the radiance that arrives along each ray of a caller-supplied batch, as

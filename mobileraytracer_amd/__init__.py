@@ -641,6 +641,68 @@ class Renderer:
         mx = o + c * (idx + 1.0)
         return self.overlap_boxes(mn, mx, 1, fields=(field,))[field].reshape(nz, ny, nx)
 
+    # -- sweep queries -------------------------------------------------------------------
+    SWEEP_FIELDS = tuple(name for name, _, _ in _native.SWEEP_FIELDS)
+
+    def sweep_spheres_device(self, d_orig: int, d_dir: int, d_radius: int, n: int, /, *, d_dist: int = 0, d_src: int = 0,
+                             orig_stride: int = 3, dir_stride: int = 3, stream: int = 0,
+                             out_size: Optional[int] = None, **outputs: int) -> None:
+        """mrt_sweep_spheres_device: the first contact of a sphere moving along each of ``n`` rays resident in
+        device memory (centre ``orig`` + ``dir`` * t, ``dir`` not normalised; ``d_radius``: n float32).
+        ``outputs``: ``d_hit``, ``d_kind``, ``d_index``, ``d_tests`` (n int32), ``d_t`` (n float32),
+        ``d_centre`` / ``d_point`` (n x 3), ``d_bary`` (n x 2) - device pointers as ints to packed arrays
+        (mrt_sweeps), 0 or absent: not wanted.  With ``d_hit`` alone (``d_tests`` aside) the walk stops at a
+        ray's first acceptance.  ``d_dist``: the bound on t per ray (n float32), 0: unbounded.  ``d_src``,
+        strides, ``out_size`` and ``stream`` as for nearest_points_device and cast_rays_device."""
+        out = _native.MrtSweeps()
+        for key, value in outputs.items():
+            if not key.startswith("d_") or key[2:] not in self.SWEEP_FIELDS:
+                raise TypeError("sweep_spheres_device: unknown output %r" % key)
+            setattr(out, key[2:], value or None)
+        batch = _native.MrtRayBatch(d_orig or None, d_dir or None, d_dist or None, d_src or None, int(orig_stride),
+                                    int(dir_stride), int(n))
+        size = ctypes.sizeof(out) if out_size is None else int(out_size)
+        _native.check(self._lib.mrt_sweep_spheres_device(self._h, ctypes.byref(batch), ctypes.c_void_p(d_radius or None),
+                                                         ctypes.byref(out), size, ctypes.c_void_p(stream or None)))
+
+    def sweep_spheres(self, orig, dirs, radius, max_t=None, src=None, fields=None):
+        """sweep_spheres_device for torch tensors on the renderer's device, with cast_rays' handling of
+        ``orig`` / ``dirs`` / ``src`` and its stream joining; ``radius`` float32 (n,), ``max_t`` float32 (n,) or
+        None (unbounded).  Returns a dict of tensors, one per name in ``fields`` (None: all of
+        ``Renderer.SWEEP_FIELDS``): int32 ``hit`` / ``kind`` / ``index`` / ``tests`` (n,), float32 ``t`` (n,),
+        ``centre`` / ``point`` (n, 3) and ``bary`` (n, 2), allocated and ordered on torch's current stream.
+        ``fields=("hit",)`` is the "is this move free" test.  An empty batch returns empty tensors."""
+        import torch
+
+        device, n, orig, orig_stride, dirs, dir_stride = self._ray_tensors(orig, dirs)
+        fields = self.SWEEP_FIELDS if fields is None else tuple(fields)
+        if not fields or any(f not in self.SWEEP_FIELDS for f in fields):
+            raise ValueError("fields: at least one of %s" % (self.SWEEP_FIELDS,))
+        if radius.device != device or radius.shape != (n,):
+            raise ValueError("radius: a tensor of shape (%d,) on %s" % (n, device))
+        radius = radius.to(torch.float32).contiguous()
+        if max_t is not None:
+            if max_t.device != device or max_t.shape != (n,):
+                raise ValueError("max_t: a tensor of shape (%d,) on %s" % (n, device))
+            max_t = max_t.to(torch.float32).contiguous()
+        if src is not None:
+            if src.device != device or src.shape != (n, 2):
+                raise ValueError("src: a tensor of shape (%d, 2) on %s" % (n, device))
+            src = src.to(torch.int32).contiguous()
+        out = {}
+        for name, dtype, width in _native.SWEEP_FIELDS:
+            if name in fields:
+                out[name] = torch.empty(n if width == 1 else (n, width), dtype=getattr(torch, dtype), device=device)
+        if n == 0:
+            return out
+        with self._query_stream_of(device) as stream:
+            self.sweep_spheres_device(orig.data_ptr(), dirs.data_ptr(), radius.data_ptr(), n,
+                                      d_dist=max_t.data_ptr() if max_t is not None else 0,
+                                      d_src=src.data_ptr() if src is not None else 0, orig_stride=orig_stride,
+                                      dir_stride=dir_stride, stream=stream,
+                                      **{"d_" + name: x.data_ptr() for name, x in out.items()})
+        return out
+
     def first_hit_planes(self, camera=None, sample: int = 0, fields=None):
         """The first hit of every pixel's camera ray (sample ``sample``) as planes: camera_rays(camera,
         sample_base=sample, spp=1), then cast_hits, scattered by ``pixels`` into (height, width) or
@@ -1011,6 +1073,32 @@ def box_overlap(kind, prims, boxes):
 def kat_box_overlap(kind, prims, boxes):
     """The same pairs through the device's overlap functions (needs a GPU)."""
     return _box_overlap(_native.lib().mrt_kat_box_overlap, kind, prims, boxes)
+
+
+def _sphere_sweep(fn, kind, prims, rays):
+    kind = int(kind)
+    width = {1: 6, 2: 4, 3: 9, 4: 9}.get(kind, 9)
+    pr = np.ascontiguousarray(prims, np.float32).reshape(-1, width)
+    ry = np.ascontiguousarray(rays, np.float32).reshape(-1, 7)
+    if len(pr) != len(ry):
+        raise ValueError("sphere_sweep: as many primitives as sweeps")
+    n = len(ry)
+    hit, t = np.empty(n, np.int32), np.empty(n, np.float32)
+    centre, point, bary = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32), np.empty((n, 2), np.float32)
+    _native.check(fn(kind, _ptr(pr), _ptr(ry), n, _ptr(hit), _ptr(t), _ptr(centre), _ptr(point), _ptr(bary)))
+    return hit, t, centre, point, bary
+
+
+def sphere_sweep(kind, prims, rays):
+    """mrt_sphere_sweep (host, no GPU): the sweep query's functions on (primitive, sweep) pairs.  kind and
+    prims as for point_distance; rays (n, 7): o xyz, d xyz, r.  Returns (hit int32 (n,), t float32 (n,) - +inf on
+    a miss, centre (n, 3), point (n, 3), bary (n, 2))."""
+    return _sphere_sweep(_native.lib().mrt_sphere_sweep, kind, prims, rays)
+
+
+def kat_sphere_sweep(kind, prims, rays):
+    """The same pairs through the device's sweep functions (needs a GPU)."""
+    return _sphere_sweep(_native.lib().mrt_kat_sphere_sweep, kind, prims, rays)
 
 
 def kat_accumulate(rgb, spp, sample_base, bitmap, width, height, mode=0):

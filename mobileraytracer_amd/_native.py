@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "mrt_cast_hits_device", "mrt_cast_multi_hits_device", "mrt_scene_triangles", "mrt_scene_planes", "mrt_scene_spheres", "mrt_scene_materials",
     "mrt_scene_lights", "mrt_nearest_points_device", "mrt_point_distance", "mrt_kat_point_distance",
     "mrt_neighbours_device", "mrt_overlap_boxes_device", "mrt_box_overlap", "mrt_kat_box_overlap",
+    "mrt_sweep_spheres_device", "mrt_sphere_sweep", "mrt_kat_sphere_sweep",
     "RayTrace", "stopRender",
 )
 
@@ -128,6 +129,15 @@ class MrtBoxBatch(ctypes.Structure):  # mrt_box_batch: a device-resident batch o
 
 class MrtOverlaps(ctypes.Structure):  # mrt_overlaps: device arrays of an overlap query, NULL = not wanted
     _fields_ = [(name, ctypes.c_void_p) for name, _, _ in OVERLAP_FIELDS]
+
+
+# mrt_sweeps: the fields in the header's order, (name, dtype, floats or ints per ray)
+SWEEP_FIELDS = (("hit", "int32", 1), ("kind", "int32", 1), ("index", "int32", 1), ("t", "float32", 1),
+                ("centre", "float32", 3), ("point", "float32", 3), ("bary", "float32", 2), ("tests", "int32", 1))
+
+
+class MrtSweeps(ctypes.Structure):  # mrt_sweeps: device arrays of a sweep query, NULL = not wanted
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in SWEEP_FIELDS]
 
 
 class MrtShadeBatch(ctypes.Structure):  # mrt_shade_batch: rays and their path keys (mrt_shade_rays_device)
@@ -282,6 +292,9 @@ def load_library(path=LIB_PATH):
                                                     ctypes.c_size_t, vp]),
         "mrt_box_overlap": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int64, vp]),
         "mrt_kat_box_overlap": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int32, vp]),
+        "mrt_sweep_spheres_device": (ctypes.c_int, [vp, P(MrtRayBatch), vp, P(MrtSweeps), ctypes.c_size_t, vp]),
+        "mrt_sphere_sweep": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int64, vp, vp, vp, vp, vp]),
+        "mrt_kat_sphere_sweep": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp]),
         "mrt_point_distance": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int64, vp, vp, vp]),
         "mrt_kat_point_distance": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int32, vp, vp, vp]),
         "mrt_scene_triangles": (ctypes.c_int64, [vp, vp, vp, vp, vp]),
@@ -319,7 +332,7 @@ def source_stamp():
     srcs = ["mrt_scene.cpp", "mrt_grid.cpp", "mrt_texture.cpp", "mrt_android.cpp", "mrt_queue_plan.cpp", "mrt_kernels.hip",
             "mrt_renderer.hip",
             "mrt_common.hpp", "mrt_device.hpp", "mrt_kernels.hpp", "mrt_trace_ww.hpp", "mrt_trace_packet.hpp",
-            "mrt_multi_hit.hpp", "mrt_nearest.hpp", "mrt_neighbours.hpp", "mrt_overlap.hpp", "mrt_scene.hpp", "mrt_queue_plan.hpp", "../../include/mobilert_amd.h", "../../include/mobilert_amd.hpp",
+            "mrt_multi_hit.hpp", "mrt_nearest.hpp", "mrt_neighbours.hpp", "mrt_overlap.hpp", "mrt_sweep.hpp", "mrt_scene.hpp", "mrt_queue_plan.hpp", "../../include/mobilert_amd.h", "../../include/mobilert_amd.hpp",
             "../../include/mobilert_android.h"]
     h = hashlib.sha256()
     for f in srcs:

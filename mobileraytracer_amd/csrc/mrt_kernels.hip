@@ -23,6 +23,7 @@
 #include "mrt_nearest.hpp"
 #include "mrt_neighbours.hpp"
 #include "mrt_overlap.hpp"
+#include "mrt_sweep.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1812,6 +1813,86 @@ __global__ __launch_bounds__(64) void k_kat_box_overlap(int kind, const float* p
 
 void launchKatBoxOverlap(int kind, const float* prims, const float* boxes, int n, int32_t* out, hipStream_t st) {
     hipLaunchKernelGGL(k_kat_box_overlap, dim3((n + 63) / 64), dim3(64), 0, st, kind, prims, boxes, n, out);
+}
+
+// ---------------------------------------------------------------------------------------
+// Sweep queries (mrt_sweep_spheres_device).  k_sweep_walk: k_neighbour_walk's frame - one ray per lane, a
+// wave taking 64 rays at a time from level 1's fetch cursor, the lane reading its radius and bound from the
+// caller's arrays and writing the caller's arrays itself - around the walk of mrt_sweep.hpp.  The stack is
+// the keyed one (a child's reference and its entry parameter, 8 B): 8 entries per lane in LDS, 4 KB per
+// one-wave workgroup, deeper entries in the closest-hit walk's spill area.  kHit: only `hit` is wanted, so
+// the walk stops at the lane's first acceptance.  Nothing accepted: hit 0, kind 0, index -1, t = the bound,
+// centre and point 0, 0, 0, bary 0, 0.
+template <bool kHit>
+__global__ __launch_bounds__(kSweepThreads) void k_sweep_walk(DScene s, Level lv, int* counters, int2* gstack, int gdepth,
+                                                              QueryTables tb, const float* radius, const float* dist,
+                                                              long long base, Sweeps out) {
+    __shared__ int2 ldsStack[kLdsStackMin * kSweepThreads];
+    TStack st = makeKeyStack<kSweepThreads>(ldsStack, gstack, gdepth);
+    const SegMap map = segMap(counters, 1, false, lv.segCap);
+    int* fetch = counters + kCntFetchShards + 1 * kMaxFetchShards * kFetchStride;
+    while (true) {
+        int first = 0;
+        if (laneId() == 0) first = atomicAdd(fetch, 64);
+        first = __shfl(first, 0, 64);
+        if (first >= map.total()) break;
+        const int v = first + laneId();
+        if (v < map.total()) {
+            const int i = map.phys(v);
+            const long long g = base + i;  // the ray's index in the caller's batch (k_query_load put it at i)
+            const float4 d4 = lv.rD[i];
+            float bound = __builtin_inff();
+            if (dist != nullptr) {
+                const float b = dist[g];
+                bound = b > 0.0F ? b : 0.0F;  // (a NaN bound finds nothing)
+            }
+            const SweepBest sb = sweepRay<kHit>(s, tb, xyz(lv.rO[i]), xyz(d4), radius[g], bound, fbits(d4.w), st);
+            const bool held = sb.code != kNoPrim;
+            if (out.hit != nullptr) out.hit[g] = held ? 1 : 0;
+            if (out.tests != nullptr) out.tests[g] = sb.tests;
+            if (!kHit) {
+                if (out.kind != nullptr) out.kind[g] = static_cast<int32_t>(primKind(sb.code));
+                if (out.index != nullptr) out.index[g] = held ? nearestInput(tb, sb.code) : -1;
+                if (out.t != nullptr) out.t[g] = sb.t;
+                store3(out.centre, g, sb.c);
+                store3(out.point, g, sb.q);
+                store2(out.bary, g, sb.u, sb.v);
+            }
+        }
+    }
+}
+
+void launchSweepWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth, const QueryTables& tb,
+                     const float* radius, const float* dist, long long base, int n, const Sweeps& out, int maxThreads,
+                     hipStream_t st) {
+    // a persistent grid over the fetch cursor: a wave per 64 rays, at most the threads the spill area holds
+    const dim3 blocks(std::max(1, std::min(maxThreads / kSweepThreads, (n + kSweepThreads - 1) / kSweepThreads)));
+    const bool hitOnly = out.kind == nullptr && out.index == nullptr && out.t == nullptr && out.centre == nullptr &&
+                         out.point == nullptr && out.bary == nullptr;
+#define MRT_LAUNCH_SWEEP(HIT) \
+    hipLaunchKernelGGL(k_sweep_walk<HIT>, blocks, dim3(kSweepThreads), 0, st, s, lv, counters, gstack, gdepth, tb, radius, dist, base, out)
+    if (hitOnly) MRT_LAUNCH_SWEEP(true);
+    else MRT_LAUNCH_SWEEP(false);
+#undef MRT_LAUNCH_SWEEP
+}
+
+__global__ __launch_bounds__(64) void k_kat_sphere_sweep(int kind, const float* prims, const float* rays, int n,
+                                                         int32_t* hit, float* t, float* centre, float* point,
+                                                         float* bary) {
+    const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const SweepHit h = sweepPrim(kind, prims + static_cast<long long>(i) * pointPrimFloats(kind), rays + 7LL * i);
+    if (hit != nullptr) hit[i] = h.hit ? 1 : 0;
+    if (t != nullptr) t[i] = h.t;
+    store3(centre, i, h.hit ? h.c : v3{0.0F, 0.0F, 0.0F});
+    store3(point, i, h.hit ? h.pd.q : v3{0.0F, 0.0F, 0.0F});
+    store2(bary, i, h.hit ? h.pd.u : 0.0F, h.hit ? h.pd.v : 0.0F);
+}
+
+void launchKatSphereSweep(int kind, const float* prims, const float* rays, int n, int32_t* hit, float* t, float* centre,
+                          float* point, float* bary, hipStream_t st) {
+    hipLaunchKernelGGL(k_kat_sphere_sweep, dim3((n + 63) / 64), dim3(64), 0, st, kind, prims, rays, n, hit, t, centre,
+                       point, bary);
 }
 
 __global__ __launch_bounds__(64) void k_kat_point_distance(int kind, const float* prims, const float* points, int n,

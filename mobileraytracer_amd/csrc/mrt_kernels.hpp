@@ -405,6 +405,29 @@ void launchOverlapWalk(const DScene& s, const Level& lv, int* counters, int2* gs
 // known answers: pair i (kind's record at prims + i * pointPrimFloats(kind), box at boxes + 6 i) through the
 // device's overlap functions
 void launchKatBoxOverlap(int kind, const float* prims, const float* boxes, int n, int32_t* out, hipStream_t st);
+// Sweep queries (mrt_sweep_spheres_device): the device arrays of mrt_sweeps, packed (ray g's hit, kind, index,
+// t and tests at g, its centre and contact point at 3 g, its bary at 2 g) or null (not wanted: not stored).
+struct Sweeps {
+    int32_t* hit;
+    int32_t* kind;
+    int32_t* index;
+    float* t;
+    float* centre;  // 3
+    float* point;   // 3
+    float* bary;    // 2
+    int32_t* tests;
+};
+// k_sweep_walk (mrt_sweep.hpp): the n rays k_query_load put into lv's queue (rD.w the mapped source) swept
+// with the radius at radius[base + i] up to dist[base + i] (dist null: unbounded) and stored by the walk at
+// base + i, indices mapped to input order through tb.  Where only hit is wanted (tests aside) the walk stops
+// at a lane's first acceptance; the spill area is the closest-hit walk's.
+void launchSweepWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth, const QueryTables& tb,
+                     const float* radius, const float* dist, long long base, int n, const Sweeps& out, int maxThreads,
+                     hipStream_t st);
+// known answers: pair i (kind's record at prims + i * pointPrimFloats(kind), sweep o, d, r at rays + 7 i)
+// through the device's sweep functions
+void launchKatSphereSweep(int kind, const float* prims, const float* rays, int n, int32_t* hit, float* t, float* centre,
+                          float* point, float* bary, hipStream_t st);
 // known answers: pair i (kind's record at prims + i * pointPrimFloats(kind), point at points + 3 i)
 // through the device's distance functions
 void launchKatPointDistance(int kind, const float* prims, const float* points, int n, float* dist2, float* nearest,

@@ -28,6 +28,7 @@
 #include "mrt_kernels.hpp"
 #include "mrt_nearest.hpp"
 #include "mrt_overlap.hpp"
+#include "mrt_sweep.hpp"
 #include "mrt_queue_plan.hpp"
 #include "mrt_scene.hpp"
 
@@ -2193,6 +2194,53 @@ void overlapBoxes(mrt_renderer* r, mrt::QueryRays q, int64_t n, int K, const mrt
                 });
 }
 
+// ---- sweep queries (mrt_sweep_spheres_device) --------------------------------------------------
+// The argument checks, as checkPointBatch's: the batch, the radii and the outputs before the renderer is read.
+mrt::QueryRays checkSweepBatch(const mrt_renderer* r, const mrt_ray_batch* rays, const float* dRadius, const mrt_sweeps* out,
+                               size_t outSize, mrt::Sweeps* sw) {
+    if (r == nullptr) throw std::runtime_error("mrt_sweep_spheres_device: null renderer");
+    if (rays == nullptr) throw std::runtime_error("mrt_sweep_spheres_device: null ray batch");
+    if (rays->orig == nullptr || rays->dir == nullptr) throw std::runtime_error("mrt_sweep_spheres_device: null orig / dir");
+    if (dRadius == nullptr) throw std::runtime_error("mrt_sweep_spheres_device: null d_radius");
+    if (out == nullptr) throw std::runtime_error("mrt_sweep_spheres_device: null outputs");
+    if (outSize < offsetof(mrt_sweeps, hit) + sizeof(out->hit))
+        throw std::runtime_error("mrt_sweep_spheres_device: outSize too small to hold hit");
+    static_assert(sizeof(mrt_sweeps) == 8 * sizeof(void*), "mrt_sweeps: pointers only (fields are appended)");
+    mrt_sweeps o{};
+    std::memcpy(&o, out, std::min(outSize, sizeof(o)) / sizeof(void*) * sizeof(void*));
+    *sw = mrt::Sweeps{o.hit, o.kind, o.index, o.t, o.centre, o.point, o.bary, o.tests};
+    if (o.hit == nullptr && o.kind == nullptr && o.index == nullptr && o.t == nullptr && o.centre == nullptr &&
+        o.point == nullptr && o.bary == nullptr && o.tests == nullptr)
+        throw std::runtime_error("mrt_sweep_spheres_device: no output (every field within outSize is null)");
+    if (rays->n < 1 || rays->n > 0x7fffffffLL) throw std::runtime_error("mrt_sweep_spheres_device: n must be 1 .. 2^31 - 1");
+    auto stride = [](int64_t s, const char* name) -> long long {
+        if (s == 0) return 3;
+        if (s < 3) throw std::runtime_error(std::string("mrt_sweep_spheres_device: ") + name + " must be 0 (packed) or >= 3 floats");
+        return s;
+    };
+    mrt::QueryRays q{};
+    q.orig = rays->orig;
+    q.dir = rays->dir;
+    q.dist = rays->dist;
+    q.src = rays->src;
+    q.origStride = stride(rays->origStride, "origStride");
+    q.dirStride = stride(rays->dirStride, "dirStride");
+    if (!r->peers.empty()) throw std::runtime_error("mrt_sweep_spheres_device: device groups are not supported for queries");
+    if (r->ds.accel == mrt::kAccGrid)
+        throw std::runtime_error("mrt_sweep_spheres_device: the RegularGrid accelerator (2) is not supported: the grid "
+                                 "has no hierarchy to bound a sweep with");
+    return q;
+}
+
+void sweepSpheres(mrt_renderer* r, mrt::QueryRays q, int64_t n, const float* dRadius, const mrt::Sweeps& out) {
+    pointChunks(r, q, n, "mrt_sweep_spheres_device",
+                [&](const mrt::Level& lv, const mrt::QueryTables& tb, const float* dist, int64_t base, int m, int threads,
+                    hipStream_t st) {
+                    mrt::launchSweepWalk(r->ds, lv, r->pipe.counters, r->pipe.gstack, r->gdepth, tb, dRadius, dist, base, m,
+                                         out, threads, st);
+                });
+}
+
 // ---- shaded ray queries (mrt_shade_rays_device) ------------------------------------------------
 // The argument checks, all before any device work, in checkRayBatch's order: the batch and the
 // output first (those checks do not read the renderer).
@@ -2551,6 +2599,26 @@ int mrt_overlap_boxes_device(mrt_renderer* r, const mrt_box_batch* boxes, int32_
             MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
         }
         overlapBoxes(r, q, boxes->n, K, ov);
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinOut, r->stream));
+            MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
+        }
+    });
+}
+
+int mrt_sweep_spheres_device(mrt_renderer* r, const mrt_ray_batch* rays, const float* dRadius, const mrt_sweeps* out,
+                             size_t outSize, void* stream) {
+    return guarded([&] {
+        mrt::Sweeps sw{};
+        const mrt::QueryRays q = checkSweepBatch(r, rays, dRadius, out, outSize, &sw);
+        MRT_HIP(hipSetDevice(r->device));
+        hipStream_t st = stream != nullptr ? static_cast<hipStream_t>(stream) : r->stream;
+        // joined to the caller's stream on both sides, as mrt_cast_rays_device
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinIn, st));
+            MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
+        }
+        sweepSpheres(r, q, rays->n, dRadius, sw);
         if (st != r->stream) {
             MRT_HIP(hipEventRecord(r->joinOut, r->stream));
             MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
@@ -3356,6 +3424,47 @@ int mrt_kat_box_overlap(int32_t kind, const float* prims, const float* boxes, in
         mrt::launchKatBoxOverlap(kind, p.as<float>(), b.as<float>(), n, o.as<int32_t>(), nullptr);
         MRT_HIP(hipGetLastError());
         MRT_HIP(hipMemcpy(out, o.p, N * 4, hipMemcpyDeviceToHost));
+        MRT_HIP(hipDeviceSynchronize());
+    });
+}
+
+int mrt_sphere_sweep(int32_t kind, const float* prims, const float* rays, int64_t n, int32_t* hit, float* t, float* centre,
+                     float* point, float* bary) {
+    return guarded([&] {
+        checkPointPairs("mrt_sphere_sweep", kind, prims, rays, n);
+        const int w = mrt::pointPrimFloats(kind);
+        const mrt::v3 zero{0.0F, 0.0F, 0.0F};
+        for (int64_t i = 0; i < n; ++i) {
+            const mrt::SweepHit h = mrt::sweepPrim(kind, prims + i * w, rays + 7 * i);
+            if (hit != nullptr) hit[i] = h.hit ? 1 : 0;
+            if (t != nullptr) t[i] = h.t;
+            if (centre != nullptr) put3(centre + 3 * i, h.hit ? h.c : zero);
+            if (point != nullptr) put3(point + 3 * i, h.hit ? h.pd.q : zero);
+            if (bary != nullptr) {
+                bary[2 * i] = h.hit ? h.pd.u : 0.0F;
+                bary[2 * i + 1] = h.hit ? h.pd.v : 0.0F;
+            }
+        }
+    });
+}
+
+int mrt_kat_sphere_sweep(int32_t kind, const float* prims, const float* rays, int32_t n, int32_t* hit, float* t,
+                         float* centre, float* point, float* bary) {
+    return guarded([&] {
+        checkPointPairs("mrt_kat_sphere_sweep", kind, prims, rays, n);
+        if (n == 0) return;
+        const size_t N = static_cast<size_t>(n), w = static_cast<size_t>(mrt::pointPrimFloats(kind));
+        DevBuf b(N * w * 4), ry(N * 28), h(N * 4), tt(N * 4), c(N * 12), q(N * 12), uv(N * 8);
+        MRT_HIP(hipMemcpy(b.p, prims, N * w * 4, hipMemcpyHostToDevice));
+        MRT_HIP(hipMemcpy(ry.p, rays, N * 28, hipMemcpyHostToDevice));
+        mrt::launchKatSphereSweep(kind, b.as<float>(), ry.as<float>(), n, h.as<int32_t>(), tt.as<float>(), c.as<float>(),
+                                  q.as<float>(), uv.as<float>(), nullptr);
+        MRT_HIP(hipGetLastError());
+        if (hit != nullptr) MRT_HIP(hipMemcpy(hit, h.p, N * 4, hipMemcpyDeviceToHost));
+        if (t != nullptr) MRT_HIP(hipMemcpy(t, tt.p, N * 4, hipMemcpyDeviceToHost));
+        if (centre != nullptr) MRT_HIP(hipMemcpy(centre, c.p, N * 12, hipMemcpyDeviceToHost));
+        if (point != nullptr) MRT_HIP(hipMemcpy(point, q.p, N * 12, hipMemcpyDeviceToHost));
+        if (bary != nullptr) MRT_HIP(hipMemcpy(bary, uv.p, N * 8, hipMemcpyDeviceToHost));
         MRT_HIP(hipDeviceSynchronize());
     });
 }
