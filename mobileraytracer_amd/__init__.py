@@ -791,9 +791,11 @@ class Renderer:
         if n == 0:
             return orig, dirs, keys, pixels
         view = self._views([camera]) if camera is not None else None
-        got = self._lib.mrt_camera_rays_device(self._h, view, int(sample_base), spp, orig.data_ptr(), dirs.data_ptr(),
-                                               keys.data_ptr(), pixels.data_ptr(),
-                                               ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream or None))
+        # (ordered on torch's current stream as the other queries are: handle 0 would be the renderer's
+        # own stream, and a reader on torch's null stream could then see the tensors before the kernel ran)
+        with self._query_stream_of(device) as stream:
+            got = self._lib.mrt_camera_rays_device(self._h, view, int(sample_base), spp, orig.data_ptr(), dirs.data_ptr(),
+                                                   keys.data_ptr(), pixels.data_ptr(), ctypes.c_void_p(stream or None))
         if got != n:
             _native.check(-1 if got < 0 else 0)
             raise RuntimeError("mrt_camera_rays_device returned %d paths, %d expected" % (got, n))

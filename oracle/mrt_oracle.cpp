@@ -15,8 +15,12 @@
 // TestCameraLoader.cpp, the triangle/light-count KAT of scripts/test/docker/dockerfile.sh
 // (CornellBox-Water 7088 faces / 2 lights), and glibc's std::partition (the BVH build uses a
 // restated libstdc++ partition, checked against std::partition by oracle_selftest_partition).
-// glm 1.0.1 and tinyobjloader v1.0.7 arithmetic is restated; radiance
-// values have no reference golden image, i.e. beyond the KATs above parity is unpinned.
+// glm 1.0.1 and tinyobjloader v1.0.7 arithmetic is restated.  The reference
+// holds no golden image, but its core does compile against the stand-in headers of oracle/refshim/
+// (oracle/ref_build.py): frames, ray batches, builds, camera rays, primitive tests and the pixel
+// conversion recorded from it are fixtures in tests/golden/reference/ that this file must reproduce
+// bit for bit (tests/test_reference_fixtures_cpu.py).  Unpinned beyond that: what draws from the
+// sample tables (area lights, PathTracer, spp > 1), the loader and textures.
 //
 // Deliberate deviations from the reference, identical in the product:
 //   * sample tables use fixed seeds and every draw is a pure function of
@@ -1287,6 +1291,7 @@ struct Engine {
     // the PathTracer's Russian roulette, one per area light.  Results then depend on thread
     // scheduling, as the reference's do.
     bool faithful = false;
+    float pixelValue = 0.5F;  // the Constant pixel sampler's value (C_wrapper.cpp:144-148: 0.5)
     mutable std::atomic<uint32_t> curHemi{0}, curLight{0}, curPixel{0}, curRR{0};
     mutable std::vector<std::atomic<uint32_t>> curArea = std::vector<std::atomic<uint32_t>>(64);
     uint32_t draw(uint32_t key, uint32_t tc, uint32_t purpose, std::atomic<uint32_t>& cursor) const {
@@ -1555,7 +1560,7 @@ struct Engine {
         const float invImgWidth = 1.0F / W, invImgHeight = 1.0F / H;
         const float pixelWidth = 0.5F / W, pixelHeight = 0.5F / H;
         const uint32_t key = pathKey(static_cast<uint32_t>(y * W + x), static_cast<uint32_t>(sample));
-        float r1 = 0.5F, r2 = 0.5F;  // Constant(0.5) unless spp > 1 (C_wrapper.cpp:144-148)
+        float r1 = pixelValue, r2 = pixelValue;  // Constant(0.5) unless spp > 1 (C_wrapper.cpp:144-148)
         if (cfg.samplesPixel > 1) {
             r1 = samplerTable[draw(key, 0u, P_JITTER_U, curPixel)];
             r2 = samplerTable[draw(key, 0u, P_JITTER_V, curPixel)];
@@ -1721,6 +1726,8 @@ int64_t oracle_regular_grid(void* h, int kind, float* world, int32_t* start, int
 
 // timing-faithful sample draws (shared atomic cursors, as the reference): 1 on, 0 off
 void oracle_set_faithful(void* h, int on) { static_cast<oracle::Engine*>(h)->faithful = on != 0; }
+// the value of the Constant pixel sampler of 1 spp frames and camera rays (the reference's is 0.5)
+void oracle_set_pixel_value(void* h, float value) { static_cast<oracle::Engine*>(h)->pixelValue = value; }
 
 int oracle_num_tiles(void* h) { return static_cast<int>(static_cast<oracle::Engine*>(h)->tiles().size()); }
 
@@ -1950,6 +1957,17 @@ int oracle_kat_plane(const float* point, const float* normal, const float* orig,
     Intersection it(ray);
     const float last = it.length;
     it = p.intersect(it);
+    *tOut = it.length;
+    return it.length < last ? 1 : 0;
+}
+
+int oracle_kat_sphere(const float* center, float radius, const float* orig, const float* dir, float* tOut) {
+    using namespace oracle;
+    const Sphere sp(Vec3(center[0], center[1], center[2]), radius, -1);
+    Ray ray(Vec3(dir[0], dir[1], dir[2]), Vec3(orig[0], orig[1], orig[2]), 1, false, nullptr, nullptr);
+    Intersection it(ray);
+    const float last = it.length;
+    it = sp.intersect(it);
     *tOut = it.length;
     return it.length < last ? 1 : 0;
 }

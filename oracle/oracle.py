@@ -60,6 +60,8 @@ def lib():
         L.oracle_triangle_aabb.argtypes = [f, f, f, f, f]
         L.oracle_kat_plane.argtypes = [f, f, f, f, f]
         L.oracle_plane_aabb.argtypes = [f, f, f, f]
+        L.oracle_kat_sphere.argtypes = [f, ctypes.c_float, f, f, f]
+        L.oracle_set_pixel_value.argtypes = [vp, ctypes.c_float]
         L.oracle_kat_camera.argtypes = [ctypes.c_char_p, ctypes.c_float, f]
         L.oracle_halton.restype = ctypes.c_float
         L.oracle_halton.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
@@ -204,6 +206,10 @@ class Oracle:
         depend on thread scheduling, as the reference's do)."""
         lib().oracle_set_faithful(self._h, int(on))
 
+    def set_pixel_value(self, value=0.5):
+        """The Constant pixel sampler's value of 1 spp frames and camera rays (the reference's: 0.5)."""
+        lib().oracle_set_pixel_value(self._h, float(value))
+
     def num_tiles(self):
         return lib().oracle_num_tiles(self._h)
 
@@ -334,6 +340,12 @@ def triangle_aabb(a, b, c):
 def kat_plane(point, normal, orig, direction):
     t = ctypes.c_float()
     hit = lib().oracle_kat_plane(fvec(*point), fvec(*normal), fvec(*orig), fvec(*direction), ctypes.byref(t))
+    return bool(hit), t.value
+
+
+def kat_sphere(center, radius, orig, direction):
+    t = ctypes.c_float()
+    hit = lib().oracle_kat_sphere(fvec(*center), float(radius), fvec(*orig), fvec(*direction), ctypes.byref(t))
     return bool(hit), t.value
 
 
