@@ -34,6 +34,10 @@
  *                             (no reference call); mrt_box_overlap is its definition on the host
  *   mrt_sweep_spheres_device  the first contact of a sphere moving along each of the caller's rays (no
  *                             reference call); mrt_sphere_sweep is its definition on the host
+ *   mrt_overlap_triangles_device
+ *                             the surfaces each of the caller's triangles (or segments, or points) touches, in
+ *                             order, and their number (no reference call); mrt_triangle_overlap is its
+ *                             definition on the host
  *   mrt_scene_triangles / _planes / _spheres / _materials / _lights
  *                             Shader::getTriangles / getPlanes / getSpheres / getMaterials / getLights
  *                             (Shader.hpp:92-100) in the scene's input order
@@ -911,6 +915,63 @@ int mrt_shade_rays_device(mrt_renderer *r, const mrt_shade_batch *b, float *d_rg
  * Returns the path count (pixelSlots*spp) or -1. */
 int64_t mrt_camera_rays_device(mrt_renderer *r, const mrt_view *view, int32_t sampleBase, int32_t spp,
                                float *d_orig, float *d_dir, uint32_t *d_key, int32_t *d_pixel, void *stream);
+
+/* ---- triangle overlap queries (on the GPU; beyond the reference's entry points) ----
+ * mrt_overlap_triangles_device: for each triangle of a caller-supplied batch the surfaces of the loaded
+ * scene that it touches, and their number: the narrow phase after mrt_overlap_boxes_device's broad phase -
+ * which faces a robot link's, a tool's or a door leaf's own triangles intersect.  A query triangle whose
+ * corners coincide is a segment or a point, so the same call answers which surfaces a segment touches and
+ * which surfaces a point lies on.
+ *
+ * The definition.  A candidate is accepted when its kind's function returns true; mrt_triangle_overlap
+ * evaluates those functions on the host, and the kernels compile the same source without contraction, so
+ * the bits agree.  Triangles and area lights: triTriangle(A, AB, AC, a, b, c), a 23-axis separating-axis
+ * test (the two normals, the nine edge cross products, the twelve in-plane edge normals, which make it
+ * complete for coplanar pairs) on the corners A, A + AB, A + AC and a, b, c with slacks that keep every real
+ * intersection; planes: triPlane; spheres: triSphere, the sphere's surface (a triangle wholly inside a
+ * sphere does not touch it).  The order of operations, the slacks and their argument are written in
+ * csrc/mrt_triangle_overlap.hpp.  A corner that is not finite, on either side, accepts nothing; degenerate
+ * triangles are valid on both sides.  The contract, on valid input barring underflow: (a) if the two closed
+ * shapes intersect in exact arithmetic on the stored float32 corners, the function returns true (touching
+ * at a point or along an edge counts; every pair, both shapes degenerate included); (b) if it returns true,
+ * the two shapes are within g * 2^-24 * M of each other, M the largest |coordinate| involved, g = 64 as
+ * measured (tests/test_triangle_overlap_cpu.py pins 4 g).  (b) is claimed wherever at least one of the two
+ * shapes has nonzero area; for a pair of two degenerate shapes only (a) is claimed.
+ *
+ * Candidates, any, count, the list, its order and its padding are mrt_overlap_boxes_device's: BVH (3) and
+ * Naive (1): every plane, sphere, triangle and area light; an accelerator id that builds nothing: the area
+ * lights only; point lights never; no src.  count is not capped by K; the list is the first min(count, K)
+ * accepted candidates by kind (plane, sphere, triangle, light), then by INPUT index; padding is kind 0,
+ * index -1.  BVH and Naive agree bit for bit in every field but tests, and every entry is what
+ * mrt_triangle_overlap says of that pair.  An invalid query triangle gives any 0, count 0, every entry
+ * padding and tests 0.
+ *
+ * What the walk may skip.  Under BVH a node of the reference tree is skipped only when its box and the hull
+ * of a, b, c are apart on some axis, strict and false for NaN: triTriangle's own first step on a box that
+ * contains the scene triangle's hull (with mrt_overlap_boxes_device's exclusion of scenes that hold a NaN
+ * first corner).  Nothing finer is used: the definition is the function's acceptance, and a finer cull would
+ * make BVH and Naive disagree on the false positives (b) admits.  A long diagonal triangle has a large hull
+ * and costs accordingly; that is allowed.  With only any wanted (tests aside) the walk stops at a
+ * triangle's first acceptance; otherwise every accepted candidate is met.
+ * RegularGrid (accelerator 2) and device groups are refused: -1 with a message, nothing done.  Everything
+ * else as mrt_overlap_boxes_device: stream order and no host synchronisation; no allocation after a
+ * renderer's first query (corners a and b go through the level-1 queue, c is read from the caller's array
+ * by the walk); chunks of rayCap[0]; state; outSize.  Argument errors (a NULL handle, batch, a, b, c or out;
+ * K outside 1 .. MRT_OVERLAP_MAX; n outside 1 .. 2^31 - 1; a stride of 1, 2 or below 0; outSize too small
+ * to hold any; every field within outSize NULL) return -1 before any device work, with a message in
+ * mrt_last_error(); they are checked before the renderer is read.
+ * mrt_triangle_overlap (host only) / mrt_kat_triangle_overlap (the same pairs through the device's
+ * functions; needs a GPU): pair i of a kind - mrt_point_distance's kinds and primitive layouts - against
+ * the triangle (a xyz, b xyz, c xyz) at tris + 9 i; out[i] = 1 accepted, 0 not. */
+typedef struct mrt_triangle_batch {
+    const float *a, *b, *c;            /* device: triangle i's corners at a + i*aStride, ... */
+    int64_t aStride, bStride, cStride; /* floats, >= 3; 0 means 3.  9 with b = a + 3, c = a + 6 reads an (n, 9) array */
+    int64_t n;                         /* 1 .. 2^31 - 1 */
+} mrt_triangle_batch;
+int mrt_overlap_triangles_device(mrt_renderer *r, const mrt_triangle_batch *tris, int32_t K,
+                                 const mrt_overlaps *out, size_t outSize, void *stream);
+int mrt_triangle_overlap(int32_t kind, const float *prims, const float *tris, int64_t n, int32_t *out);     /* host only */
+int mrt_kat_triangle_overlap(int32_t kind, const float *prims, const float *tris, int32_t n, int32_t *out); /* needs a GPU */
 
 #ifdef __cplusplus
 }

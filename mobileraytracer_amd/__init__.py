@@ -641,6 +641,83 @@ class Renderer:
         mx = o + c * (idx + 1.0)
         return self.overlap_boxes(mn, mx, 1, fields=(field,))[field].reshape(nz, ny, nx)
 
+    # -- triangle overlap queries --------------------------------------------------------
+    def overlap_triangles_device(self, d_a: int, d_b: int, d_c: int, n: int, k: int, /, *, a_stride: int = 3,
+                                 b_stride: int = 3, c_stride: int = 3, stream: int = 0,
+                                 out_size: Optional[int] = None, **fields: int) -> None:
+        """mrt_overlap_triangles_device: the surfaces each of ``n`` query triangles resident in device memory
+        touches (triangle i's corners at ``d_a`` + i * ``a_stride`` floats, ``d_b`` + i * ``b_stride``,
+        ``d_c`` + i * ``c_stride``; strides of 9 with d_b = d_a + 12 bytes and d_c = d_a + 24 read an (n, 9)
+        array), the first ``k`` (1 .. 16) by kind and input index, and their number.  A triangle whose corners
+        coincide is a segment or a point.  ``fields``, ``out_size`` and ``stream`` as for
+        overlap_boxes_device."""
+        out = _native.MrtOverlaps()
+        for key, value in fields.items():
+            if not key.startswith("d_") or key[2:] not in self.OVERLAP_FIELDS:
+                raise TypeError("overlap_triangles_device: unknown output %r" % key)
+            setattr(out, key[2:], value or None)
+        batch = _native.MrtTriangleBatch(d_a or None, d_b or None, d_c or None, int(a_stride), int(b_stride),
+                                         int(c_stride), int(n))
+        size = ctypes.sizeof(out) if out_size is None else int(out_size)
+        _native.check(self._lib.mrt_overlap_triangles_device(self._h, ctypes.byref(batch), int(k), ctypes.byref(out),
+                                                             size, ctypes.c_void_p(stream or None)))
+
+    def overlap_triangles(self, tri, k: int, fields=None):
+        """overlap_triangles_device for a torch float32 tensor on the renderer's device: ``tri`` (n, 9) or
+        (n, 3, 3), the corners a, b, c of each query triangle, read in place (a contiguous tensor is not
+        copied), with cast_rays' stream joining.  Returns a dict of tensors as overlap_boxes does.  An empty
+        batch returns empty tensors."""
+        import torch
+
+        if not hasattr(tri, "dim") or tri.dtype != torch.float32 or not (
+                (tri.dim() == 2 and tri.shape[1] == 9) or (tri.dim() == 3 and tuple(tri.shape[1:]) == (3, 3))):
+            raise ValueError("tri: a float32 tensor of shape (n, 9) or (n, 3, 3)")
+        n = tri.shape[0]
+        rows = tri.reshape(n, 9)
+        if rows.stride(1) != 1 or (n > 1 and rows.stride(0) < 9):
+            rows = rows.contiguous()
+        stride = rows.stride(0) if n > 1 else 9
+        device, n, a, _, b, _ = self._ray_tensors(rows[:, 0:3], rows[:, 3:6])
+        k = int(k)
+        if not 1 <= k <= _native.OVERLAP_MAX:
+            raise ValueError("k: 1 .. %d" % _native.OVERLAP_MAX)
+        fields = self.OVERLAP_FIELDS if fields is None else tuple(fields)
+        if not fields or any(f not in self.OVERLAP_FIELDS for f in fields):
+            raise ValueError("fields: at least one of %s" % (self.OVERLAP_FIELDS,))
+        out = {}
+        for name, dtype, width in _native.OVERLAP_FIELDS:
+            if name in fields:
+                out[name] = torch.empty((n,) if width == 0 else (n, k), dtype=getattr(torch, dtype), device=device)
+        if n == 0:
+            return out
+        with self._query_stream_of(device) as stream:
+            base = rows.data_ptr()
+            self.overlap_triangles_device(base, base + 12, base + 24, n, k, a_stride=stride, b_stride=stride,
+                                          c_stride=stride, stream=stream,
+                                          **{"d_" + name: x.data_ptr() for name, x in out.items()})
+        return out
+
+    def overlap_mesh(self, vertices, faces, k: int, fields=None, transform=None):
+        """overlap_triangles for the triangles of a mesh: ``vertices`` float32 (v, 3) and ``faces`` integer
+        (n, 3) tensors on the renderer's device; query triangle i has the corners ``vertices[faces[i]]``.
+        With a 4 x 4 ``transform`` (a tensor, or anything torch.as_tensor takes) the vertices are first moved:
+        ``vertices @ R.T + t`` in torch float32, R the upper-left 3 x 3 and t the last column.  The transformed
+        corners' bits are torch's (its matrix product's order of operations, not this library's), and the
+        answer is defined on the corners the query is given: it is overlap_triangles of exactly those floats."""
+        import torch
+
+        if not hasattr(vertices, "dim") or vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+            raise ValueError("vertices: a float32 tensor of shape (v, 3)")
+        if not hasattr(faces, "dim") or faces.dim() != 2 or faces.shape[1] != 3 or faces.is_floating_point():
+            raise ValueError("faces: an integer tensor of shape (n, 3)")
+        if transform is not None:
+            t = torch.as_tensor(transform, dtype=torch.float32).to(vertices.device)
+            if tuple(t.shape) != (4, 4):
+                raise ValueError("transform: 4 x 4")
+            vertices = vertices @ t[:3, :3].T + t[:3, 3]
+        tri = vertices[faces.to(device=vertices.device, dtype=torch.long)].reshape(-1, 9)
+        return self.overlap_triangles(tri, k, fields=fields)
+
     # -- sweep queries -------------------------------------------------------------------
     SWEEP_FIELDS = tuple(name for name, _, _ in _native.SWEEP_FIELDS)
 
@@ -1075,6 +1152,30 @@ def box_overlap(kind, prims, boxes):
 def kat_box_overlap(kind, prims, boxes):
     """The same pairs through the device's overlap functions (needs a GPU)."""
     return _box_overlap(_native.lib().mrt_kat_box_overlap, kind, prims, boxes)
+
+
+def _triangle_overlap(fn, kind, prims, tris):
+    kind = int(kind)
+    width = {1: 6, 2: 4, 3: 9, 4: 9}.get(kind, 9)
+    pr = np.ascontiguousarray(prims, np.float32).reshape(-1, width)
+    tr = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
+    if len(pr) != len(tr):
+        raise ValueError("triangle_overlap: as many primitives as triangles")
+    out = np.empty(len(tr), np.int32)
+    _native.check(fn(kind, _ptr(pr), _ptr(tr), len(tr), _ptr(out)))
+    return out
+
+
+def triangle_overlap(kind, prims, tris):
+    """mrt_triangle_overlap (host, no GPU): the triangle overlap query's functions on (primitive, triangle)
+    pairs.  kind and prims as for point_distance; tris (n, 9) or (n, 3, 3): the corners a, b, c.  Returns int32
+    (n,): 1 accepted, 0 not."""
+    return _triangle_overlap(_native.lib().mrt_triangle_overlap, kind, prims, tris)
+
+
+def kat_triangle_overlap(kind, prims, tris):
+    """The same pairs through the device's triangle overlap functions (needs a GPU)."""
+    return _triangle_overlap(_native.lib().mrt_kat_triangle_overlap, kind, prims, tris)
 
 
 def _sphere_sweep(fn, kind, prims, rays):

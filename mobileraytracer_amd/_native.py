@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "mrt_scene_lights", "mrt_nearest_points_device", "mrt_point_distance", "mrt_kat_point_distance",
     "mrt_neighbours_device", "mrt_overlap_boxes_device", "mrt_box_overlap", "mrt_kat_box_overlap",
     "mrt_sweep_spheres_device", "mrt_sphere_sweep", "mrt_kat_sphere_sweep",
+    "mrt_overlap_triangles_device", "mrt_triangle_overlap", "mrt_kat_triangle_overlap",
     "RayTrace", "stopRender",
 )
 
@@ -125,6 +126,11 @@ OVERLAP_FIELDS = (("any", "int32", 0), ("count", "int32", 0), ("kind", "int32", 
 class MrtBoxBatch(ctypes.Structure):  # mrt_box_batch: a device-resident batch of boxes (mrt_overlap_boxes_device)
     _fields_ = [("mn", ctypes.c_void_p), ("mx", ctypes.c_void_p), ("mnStride", ctypes.c_int64),
                 ("mxStride", ctypes.c_int64), ("n", ctypes.c_int64)]
+
+
+class MrtTriangleBatch(ctypes.Structure):  # mrt_triangle_batch: device-resident query triangles (mrt_overlap_triangles_device)
+    _fields_ = [("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("c", ctypes.c_void_p), ("aStride", ctypes.c_int64),
+                ("bStride", ctypes.c_int64), ("cStride", ctypes.c_int64), ("n", ctypes.c_int64)]
 
 
 class MrtOverlaps(ctypes.Structure):  # mrt_overlaps: device arrays of an overlap query, NULL = not wanted
@@ -292,6 +298,10 @@ def load_library(path=LIB_PATH):
                                                     ctypes.c_size_t, vp]),
         "mrt_box_overlap": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int64, vp]),
         "mrt_kat_box_overlap": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int32, vp]),
+        "mrt_overlap_triangles_device": (ctypes.c_int, [vp, P(MrtTriangleBatch), ctypes.c_int32, P(MrtOverlaps),
+                                                        ctypes.c_size_t, vp]),
+        "mrt_triangle_overlap": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int64, vp]),
+        "mrt_kat_triangle_overlap": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int32, vp]),
         "mrt_sweep_spheres_device": (ctypes.c_int, [vp, P(MrtRayBatch), vp, P(MrtSweeps), ctypes.c_size_t, vp]),
         "mrt_sphere_sweep": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int64, vp, vp, vp, vp, vp]),
         "mrt_kat_sphere_sweep": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp]),
@@ -332,7 +342,7 @@ def source_stamp():
     srcs = ["mrt_scene.cpp", "mrt_grid.cpp", "mrt_texture.cpp", "mrt_android.cpp", "mrt_queue_plan.cpp", "mrt_kernels.hip",
             "mrt_renderer.hip",
             "mrt_common.hpp", "mrt_device.hpp", "mrt_kernels.hpp", "mrt_trace_ww.hpp", "mrt_trace_packet.hpp",
-            "mrt_multi_hit.hpp", "mrt_nearest.hpp", "mrt_neighbours.hpp", "mrt_overlap.hpp", "mrt_sweep.hpp", "mrt_scene.hpp", "mrt_queue_plan.hpp", "../../include/mobilert_amd.h", "../../include/mobilert_amd.hpp",
+            "mrt_multi_hit.hpp", "mrt_nearest.hpp", "mrt_neighbours.hpp", "mrt_overlap.hpp", "mrt_sweep.hpp", "mrt_triangle_overlap.hpp", "mrt_scene.hpp", "mrt_queue_plan.hpp", "../../include/mobilert_amd.h", "../../include/mobilert_amd.hpp",
             "../../include/mobilert_android.h"]
     h = hashlib.sha256()
     for f in srcs:

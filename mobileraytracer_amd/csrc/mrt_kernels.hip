@@ -24,6 +24,7 @@
 #include "mrt_neighbours.hpp"
 #include "mrt_overlap.hpp"
 #include "mrt_sweep.hpp"
+#include "mrt_triangle_overlap.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1813,6 +1814,81 @@ __global__ __launch_bounds__(64) void k_kat_box_overlap(int kind, const float* p
 
 void launchKatBoxOverlap(int kind, const float* prims, const float* boxes, int n, int32_t* out, hipStream_t st) {
     hipLaunchKernelGGL(k_kat_box_overlap, dim3((n + 63) / 64), dim3(64), 0, st, kind, prims, boxes, n, out);
+}
+
+// ---------------------------------------------------------------------------------------
+// Triangle overlap queries (mrt_overlap_triangles_device).  k_triangle_overlap_walk: k_overlap_walk's frame -
+// one query triangle per lane, a wave taking 64 at a time from level 1's fetch cursor, the list in LDS
+// (OverlapHeld), the lane writing the caller's arrays itself - around the walk of mrt_triangle_overlap.hpp.
+// A level-1 slot holds eight floats: k_query_load put corner a into the origin slots and corner b into the
+// direction slots, and the lane reads corner c from the caller's array at base + i with the caller's stride
+// (as k_sweep_walk reads its radius).  kCeil, kAny, K and listK as k_overlap_walk's.
+template <int kCeil, bool kAny>
+__global__ __launch_bounds__(kOverlapThreads) void k_triangle_overlap_walk(DScene s, Level lv, int* counters,
+                                                                           int2* gstack, int gdepth, QueryTables tb,
+                                                                           const float* c, long long cStride,
+                                                                           long long base, int K, int listK,
+                                                                           Overlaps out) {
+    __shared__ int ldsStack[RefStack<kOverlapThreads>::kDepth * kOverlapThreads];
+    __shared__ uint32_t olCode[kCeil * kOverlapThreads];
+    auto st = makeRefStack<kOverlapThreads>(reinterpret_cast<int2*>(ldsStack), gstack, gdepth);
+    OverlapHeld<kAny> ol{olCode + threadIdx.x, min(listK, kCeil), 0, 0, 0};
+    const SegMap map = segMap(counters, 1, false, lv.segCap);
+    int* fetch = counters + kCntFetchShards + 1 * kMaxFetchShards * kFetchStride;
+    while (true) {
+        int first = 0;
+        if (laneId() == 0) first = atomicAdd(fetch, 64);
+        first = __shfl(first, 0, 64);
+        if (first >= map.total()) break;
+        const int v = first + laneId();
+        if (v < map.total()) {
+            const int i = map.phys(v);
+            const long long g = base + i;  // the triangle's index in the caller's batch (k_query_load put it at i)
+            const float* cp = c + g * cStride;
+            const TriQuery t = triQuery(xyz(lv.rO[i]), xyz(lv.rD[i]), v3{cp[0], cp[1], cp[2]});
+            ol.reset();
+            triOverlapQuery(s, tb, t, ol, st);
+            if (out.any != nullptr) out.any[g] = ol.count != 0 ? 1 : 0;
+            if (out.tests != nullptr) out.tests[g] = ol.tests;
+            if (!kAny) {
+                if (out.count != nullptr) out.count[g] = ol.count;
+                const long long e0 = g * K;
+                for (int k = 0; k < ol.K; ++k) {
+                    const bool held = k < ol.n;
+                    const uint32_t code = held ? ol.code[k * kOverlapThreads] : kNoPrim;
+                    if (out.kind != nullptr) out.kind[e0 + k] = static_cast<int32_t>(primKind(code));
+                    if (out.index != nullptr) out.index[e0 + k] = held ? static_cast<int32_t>(primIndex(code)) : -1;
+                }
+            }
+        }
+    }
+}
+
+void launchTriangleOverlapWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth,
+                               const QueryTables& tb, const float* c, long long cStride, long long base, int n, int K,
+                               const Overlaps& out, int maxThreads, hipStream_t st) {
+    // a persistent grid over the fetch cursor: a wave per 64 triangles, at most the threads the spill area holds
+    const dim3 blocks(std::max(1, std::min(maxThreads / kOverlapThreads, (n + kOverlapThreads - 1) / kOverlapThreads)));
+    const bool list = out.kind != nullptr || out.index != nullptr;
+    const int listK = list ? K : 0;
+#define MRT_LAUNCH_TRI_OVERLAP(CEIL, ANY) \
+    hipLaunchKernelGGL((k_triangle_overlap_walk<CEIL, ANY>), blocks, dim3(kOverlapThreads), 0, st, s, lv, counters, gstack, gdepth, tb, c, cStride, base, K, listK, out)
+    if (!list && out.count == nullptr) MRT_LAUNCH_TRI_OVERLAP(1, true);
+    else if (listK <= 1) MRT_LAUNCH_TRI_OVERLAP(1, false);
+    else if (listK <= 4) MRT_LAUNCH_TRI_OVERLAP(4, false);
+    else MRT_LAUNCH_TRI_OVERLAP(kOverlapMax, false);
+#undef MRT_LAUNCH_TRI_OVERLAP
+}
+
+__global__ __launch_bounds__(64) void k_kat_triangle_overlap(int kind, const float* prims, const float* tris, int n,
+                                                             int32_t* out) {
+    const int i = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    out[i] = triOverlapPrim(kind, prims + static_cast<long long>(i) * pointPrimFloats(kind), tris + 9LL * i) ? 1 : 0;
+}
+
+void launchKatTriangleOverlap(int kind, const float* prims, const float* tris, int n, int32_t* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_kat_triangle_overlap, dim3((n + 63) / 64), dim3(64), 0, st, kind, prims, tris, n, out);
 }
 
 // ---------------------------------------------------------------------------------------

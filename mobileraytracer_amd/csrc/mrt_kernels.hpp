@@ -405,6 +405,15 @@ void launchOverlapWalk(const DScene& s, const Level& lv, int* counters, int2* gs
 // known answers: pair i (kind's record at prims + i * pointPrimFloats(kind), box at boxes + 6 i) through the
 // device's overlap functions
 void launchKatBoxOverlap(int kind, const float* prims, const float* boxes, int n, int32_t* out, hipStream_t st);
+// k_triangle_overlap_walk (mrt_triangle_overlap.hpp): the n query triangles whose corners a and b k_query_load
+// put into lv's queue (a the origins, b the directions) and whose corner c the walk reads from the caller's
+// array (triangle base + i's at c + (base + i) * cStride), answered and stored as launchOverlapWalk's boxes.
+void launchTriangleOverlapWalk(const DScene& s, const Level& lv, int* counters, int2* gstack, int gdepth,
+                               const QueryTables& tb, const float* c, long long cStride, long long base, int n, int K,
+                               const Overlaps& out, int maxThreads, hipStream_t st);
+// known answers: pair i (kind's record at prims + i * pointPrimFloats(kind), triangle at tris + 9 i) through the
+// device's triangle overlap functions
+void launchKatTriangleOverlap(int kind, const float* prims, const float* tris, int n, int32_t* out, hipStream_t st);
 // Sweep queries (mrt_sweep_spheres_device): the device arrays of mrt_sweeps, packed (ray g's hit, kind, index,
 // t and tests at g, its centre and contact point at 3 g, its bary at 2 g) or null (not wanted: not stored).
 struct Sweeps {

@@ -29,6 +29,7 @@
 #include "mrt_nearest.hpp"
 #include "mrt_overlap.hpp"
 #include "mrt_sweep.hpp"
+#include "mrt_triangle_overlap.hpp"
 #include "mrt_queue_plan.hpp"
 #include "mrt_scene.hpp"
 
@@ -2194,6 +2195,56 @@ void overlapBoxes(mrt_renderer* r, mrt::QueryRays q, int64_t n, int K, const mrt
                 });
 }
 
+// ---- triangle overlap queries (mrt_overlap_triangles_device) -----------------------------------
+// The argument checks, as checkBoxBatch's: the batch, K and the outputs before the renderer is read.  Corners a
+// and b travel as the query load's origins and directions; c and its stride go to the walk.
+mrt::QueryRays checkTriangleBatch(const mrt_renderer* r, const mrt_triangle_batch* tris, int32_t K, const mrt_overlaps* out,
+                                  size_t outSize, mrt::Overlaps* ov, long long* cStride) {
+    if (r == nullptr) throw std::runtime_error("mrt_overlap_triangles_device: null renderer");
+    if (tris == nullptr) throw std::runtime_error("mrt_overlap_triangles_device: null triangle batch");
+    if (tris->a == nullptr || tris->b == nullptr || tris->c == nullptr)
+        throw std::runtime_error("mrt_overlap_triangles_device: null a / b / c");
+    if (out == nullptr) throw std::runtime_error("mrt_overlap_triangles_device: null outputs");
+    if (K < 1 || K > MRT_OVERLAP_MAX)
+        throw std::runtime_error("mrt_overlap_triangles_device: K must be 1 .. " + std::to_string(MRT_OVERLAP_MAX));
+    if (outSize < offsetof(mrt_overlaps, any) + sizeof(out->any))
+        throw std::runtime_error("mrt_overlap_triangles_device: outSize too small to hold any");
+    mrt_overlaps o{};
+    std::memcpy(&o, out, std::min(outSize, sizeof(o)) / sizeof(void*) * sizeof(void*));
+    *ov = mrt::Overlaps{o.any, o.count, o.kind, o.index, o.tests};
+    if (o.any == nullptr && o.count == nullptr && o.kind == nullptr && o.index == nullptr && o.tests == nullptr)
+        throw std::runtime_error("mrt_overlap_triangles_device: no output (every field within outSize is null)");
+    if (tris->n < 1 || tris->n > 0x7fffffffLL)
+        throw std::runtime_error("mrt_overlap_triangles_device: n must be 1 .. 2^31 - 1");
+    auto stride = [](int64_t s) -> long long {
+        if (s == 0) return 3;
+        if (s < 3) throw std::runtime_error("mrt_overlap_triangles_device: strides must be 0 (packed) or >= 3 floats");
+        return s;
+    };
+    mrt::QueryRays q{};
+    q.orig = tris->a;
+    q.dir = tris->b;
+    q.origStride = stride(tris->aStride);
+    q.dirStride = stride(tris->bStride);
+    *cStride = stride(tris->cStride);
+    if (!r->peers.empty())
+        throw std::runtime_error("mrt_overlap_triangles_device: device groups are not supported for queries");
+    if (r->ds.accel == mrt::kAccGrid)
+        throw std::runtime_error("mrt_overlap_triangles_device: the RegularGrid accelerator (2) is not supported: the "
+                                 "region queries walk the reference tree");
+    return q;
+}
+
+void overlapTriangles(mrt_renderer* r, mrt::QueryRays q, const float* c, long long cStride, int64_t n, int K,
+                      const mrt::Overlaps& out) {
+    pointChunks(r, q, n, "mrt_overlap_triangles_device",
+                [&](const mrt::Level& lv, const mrt::QueryTables& tb, const float*, int64_t base, int m, int threads,
+                    hipStream_t st) {
+                    mrt::launchTriangleOverlapWalk(r->ds, lv, r->pipe.counters, r->pipe.gstack, r->gdepth, tb, c, cStride,
+                                                   base, m, K, out, threads, st);
+                });
+}
+
 // ---- sweep queries (mrt_sweep_spheres_device) --------------------------------------------------
 // The argument checks, as checkPointBatch's: the batch, the radii and the outputs before the renderer is read.
 mrt::QueryRays checkSweepBatch(const mrt_renderer* r, const mrt_ray_batch* rays, const float* dRadius, const mrt_sweeps* out,
@@ -2599,6 +2650,27 @@ int mrt_overlap_boxes_device(mrt_renderer* r, const mrt_box_batch* boxes, int32_
             MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
         }
         overlapBoxes(r, q, boxes->n, K, ov);
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinOut, r->stream));
+            MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
+        }
+    });
+}
+
+int mrt_overlap_triangles_device(mrt_renderer* r, const mrt_triangle_batch* tris, int32_t K, const mrt_overlaps* out,
+                                 size_t outSize, void* stream) {
+    return guarded([&] {
+        mrt::Overlaps ov{};
+        long long cStride = 3;
+        const mrt::QueryRays q = checkTriangleBatch(r, tris, K, out, outSize, &ov, &cStride);
+        MRT_HIP(hipSetDevice(r->device));
+        hipStream_t st = stream != nullptr ? static_cast<hipStream_t>(stream) : r->stream;
+        // joined to the caller's stream on both sides, as mrt_cast_rays_device
+        if (st != r->stream) {
+            MRT_HIP(hipEventRecord(r->joinIn, st));
+            MRT_HIP(hipStreamWaitEvent(r->stream, r->joinIn, 0));
+        }
+        overlapTriangles(r, q, tris->c, cStride, tris->n, K, ov);
         if (st != r->stream) {
             MRT_HIP(hipEventRecord(r->joinOut, r->stream));
             MRT_HIP(hipStreamWaitEvent(st, r->joinOut, 0));
@@ -3422,6 +3494,31 @@ int mrt_kat_box_overlap(int32_t kind, const float* prims, const float* boxes, in
         MRT_HIP(hipMemcpy(p.p, prims, N * w * 4, hipMemcpyHostToDevice));
         MRT_HIP(hipMemcpy(b.p, boxes, N * 24, hipMemcpyHostToDevice));
         mrt::launchKatBoxOverlap(kind, p.as<float>(), b.as<float>(), n, o.as<int32_t>(), nullptr);
+        MRT_HIP(hipGetLastError());
+        MRT_HIP(hipMemcpy(out, o.p, N * 4, hipMemcpyDeviceToHost));
+        MRT_HIP(hipDeviceSynchronize());
+    });
+}
+
+int mrt_triangle_overlap(int32_t kind, const float* prims, const float* tris, int64_t n, int32_t* out) {
+    return guarded([&] {
+        checkPointPairs("mrt_triangle_overlap", kind, prims, tris, n);
+        if (out == nullptr) throw std::runtime_error("mrt_triangle_overlap: null out");
+        const int w = mrt::pointPrimFloats(kind);
+        for (int64_t i = 0; i < n; ++i) out[i] = mrt::triOverlapPrim(kind, prims + i * w, tris + 9 * i) ? 1 : 0;
+    });
+}
+
+int mrt_kat_triangle_overlap(int32_t kind, const float* prims, const float* tris, int32_t n, int32_t* out) {
+    return guarded([&] {
+        checkPointPairs("mrt_kat_triangle_overlap", kind, prims, tris, n);
+        if (out == nullptr) throw std::runtime_error("mrt_kat_triangle_overlap: null out");
+        if (n == 0) return;
+        const size_t N = static_cast<size_t>(n), w = static_cast<size_t>(mrt::pointPrimFloats(kind));
+        DevBuf p(N * w * 4), b(N * 36), o(N * 4);
+        MRT_HIP(hipMemcpy(p.p, prims, N * w * 4, hipMemcpyHostToDevice));
+        MRT_HIP(hipMemcpy(b.p, tris, N * 36, hipMemcpyHostToDevice));
+        mrt::launchKatTriangleOverlap(kind, p.as<float>(), b.as<float>(), n, o.as<int32_t>(), nullptr);
         MRT_HIP(hipGetLastError());
         MRT_HIP(hipMemcpy(out, o.p, N * 4, hipMemcpyDeviceToHost));
         MRT_HIP(hipDeviceSynchronize());
